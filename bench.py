@@ -7,19 +7,24 @@ YAML enables: guidance 3, stg 1, skip block 19), N = 13*16*24 = 4992 tokens, T =
 28 layers, bf16, random-init weights of the 2B architecture, followed by the fused
 CFG-star/STG/rescale + Euler update.  `value` = steps/s over all ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up, warms up, times exactly K steps and prints the line; nothing else.  --dump-outputs DIR then
+writes what the last timed step computed as float32 .npy files (latents.npy: the updated latents, noise_pred.npy:
+the transformer's prediction for the three rows); the inputs are seeded, so two builds can be compared file for file.
+
 N > 1: one process per GPU.  `value` = replicas (every rank denoises its own video, RCCL only for the
-barrier / max-reduce of the clock; "scaling": "weak").  The same run then times the sequence-sharded mode the
-north star names (ONE video, tokens sharded over the ranks, Ulysses all-to-all inside self-attention,
+barrier / max-reduce of the clock; "scaling": "weak").  With --full the same run then times the sequence-sharded
+mode the north star names (ONE video, tokens sharded over the ranks, Ulysses all-to-all inside self-attention,
 ltxmi/distributed.py) and reports it in the same line under "ulysses" ("scaling": "strong").
-The JSON line also carries:
+The JSON line carries:
   roofline      the dominant kernel of this workload = the self-attention kernel (28 launches per step, the
                 largest single share of a step; MFMA-bound): algorithmic FLOP per launch / average launch time
                 from HIP events recorded on the launch stream inside the timed region
   roofline_gemm the same for the FF up-projection GEMM (the largest GEMM instance)
   step_ms       median / p10 / p90 of the timed steps (HIP events per step)
+and, with --full only (every leg below takes runs of its own):
   b_eff_1       the same step with ONE cond (no CFG / STG rows)
   attention     the self-attention kernel at the north-star stress shape (N = 98304, 1 layer, B = 1), at config 3's
                 N = 13376 and at config 4's Wan shape [1, 32760, 12, 128] (+ cross-attention, 512 text keys)
@@ -105,6 +110,8 @@ class StepRunner:
         self.embeds = torch.cat([neg, emb, emb])
         self.mask = torch.cat([nmask, mask, mask])
         self.device = device
+        self.keep_outputs = False                  # --dump-outputs: hold on to the last step's noise_pred
+        self.noise_pred = None
         self.set_grid(GRID)
         self.skip = self.m.create_skip_layer_mask(1, NUM_CONDS, NUM_CONDS - 1, [19])
         self.ws = torch.empty(ops.GUIDANCE_WORKSPACE_FLOATS, device=device)
@@ -160,14 +167,17 @@ class StepRunner:
                 self.m, x, self.freqs, encoder_hidden_states=self.embeds, encoder_attention_mask=self.mask,
                 timestep=self.t_dev, skip_layer_mask=self.skip,
                 skip_layer_strategy=self.ltxmi.SkipLayerStrategy.AttentionValues, latent_shape=self.grid,
-                ltxv_model=self.holder)[0]
-            self.ops.guidance_step_(noise_pred.contiguous(), self.latents, self.dt, 3.0, 1.0, 0.7, True, True, True,
-                                    self.ws)
+                ltxv_model=self.holder)[0].contiguous()
+            if self.keep_outputs:
+                self.noise_pred = noise_pred
+            self.ops.guidance_step_(noise_pred, self.latents, self.dt, 3.0, 1.0, 0.7, True, True, True, self.ws)
             return
         noise_pred = self.m(x, freqs_cis=self.freqs, encoder_hidden_states=self.embeds,
                             encoder_attention_mask=self.mask, timestep=self.t_dev, skip_layer_mask=self.skip,
                             skip_layer_strategy=self.ltxmi.SkipLayerStrategy.AttentionValues, latent_shape=self.grid,
                             ltxv_model=self.holder, return_dict=False, stg_alias_blocks=stg_alias_blocks)[0]
+        if self.keep_outputs:
+            self.noise_pred = noise_pred
         self.ops.guidance_step_(noise_pred, self.latents, self.dt, 3.0, 1.0, 0.7, True, True, True, self.ws)
 
 
@@ -753,7 +763,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-extras", action="store_true", help="skip the B_eff-1 / attention-shape / VAE / CPU legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too: B_eff 1, pipeline default, config 3, the Ulysses "
+                         "projection, the attention shapes, the VAE decodes and the CPU baselines (N = 1), the collective "
+                         "legs (N > 1); a plain run times the headline steps only")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the B_eff-1 / attention-shape / VAE / CPU legs (the Ulysses legs still run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (latents, noise_pred) as float32 DIR/<name>.npy")
     ap.add_argument("--parallelism", choices=["both", "replicas", "ulysses"], default="both",
                     help="N > 1 only.  replicas: every rank denoises its own video, no data-path collective (weak scaling, "
                          "this is `value`); ulysses: ONE video, tokens sharded over the ranks, all-to-all inside "
@@ -765,7 +782,8 @@ def main():
                          "them, and ends the ranks (they could only be run at world size 1 on hardware so far: a hang there "
                          "must not take the headline value with it)")
     ap.add_argument("--rehearse-both", action="store_true",
-                    help="run the N > 1 control flow (replicas, then Ulysses, both in the one JSON line) at world size 1")
+                    help="with --full: run the N > 1 control flow (replicas, then Ulysses, both in the one JSON line) at "
+                         "world size 1")
     ap.add_argument("--selftest-launch", action="store_true",
                     help="launcher check (CPU suite): every rank joins a gloo group, rank 0 prints {\"selftest_launch\": true, "
                          "\"n_gpus\": world}; no GPU is touched")
@@ -773,6 +791,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.rehearse_both and not args.full:
+        ap.error("--rehearse-both rehearses the collective legs, which only a --full run has")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, BEFORE anything here touches the
         # GPU (this process never initialises HIP; it only waits for its child and passes its exit code on)
@@ -935,16 +957,28 @@ def main():
                         "p90": round(pct(uly3["per_step"], 0.9), 3)},
             "attention_launch_ms": round(uly3["at_ms"], 4)}
 
+    def dump_outputs():
+        """rank 0, right after the headline's timed steps: what the last of them computed, float32."""
+        if rank == 0 and args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, t in (("latents", runner.latents), ("noise_pred", runner.noise_pred)):
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
+        runner.keep_outputs, runner.noise_pred = False, None
+
+    runner.keep_outputs = bool(args.dump_outputs)
     if ulysses_only:
         runner.enable_ulysses()
         r = measure(True)
+        dump_outputs()
         if rank == 0:
             line = build_line()
     else:
         r = measure(False)
+        dump_outputs()
         if rank == 0:
             line = build_line()
-        if (world > 1 or args.rehearse_both) and args.parallelism == "both":
+        if args.full and (world > 1 or args.rehearse_both) and args.parallelism == "both":
             # The replicas measurement above is the line's `value`.  The legs below run collectives on paths that could only be
             # run at world size 1 on hardware so far.  Two nets under them: an exception between collectives is agreed among
             # the ranks and reported (agree_failed); a HANG inside a collective ends in the watchdog, which prints the line as it
@@ -1005,7 +1039,7 @@ def main():
                     line["vae_decode_config5_tile_parallel"] = vtp
                 done["legs"].append("vae_decode_config5_tile_parallel")
             watchdog.cancel()
-    extras = (not args.no_extras) and world == 1 and not ulysses_only
+    extras = args.full and (not args.no_extras) and world == 1 and not ulysses_only
     if extras:
         # B_eff = 1 (report both): the same model, the text row only
         for _ in range(2):

@@ -58,7 +58,7 @@ def test_bench_watchdog_prints_the_replicas_line_when_the_collective_legs_hang()
     """The legs that run collectives (Ulysses, tile-parallel decode) have only ever run at world size 1 on hardware: a hang in
     them must not cost the line its `value`.  With a deadline no leg can meet, the bench still prints ONE line -- the replicas
     measurement with error entries for those legs -- and exits 0; with the default deadline the same command fills them in."""
-    cmd = [sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--no-extras", "--rehearse-both"]
+    cmd = [sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--rehearse-both"]
     r = subprocess.run(cmd + ["--collective-timeout", "0.05"], env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -71,3 +71,32 @@ def test_bench_watchdog_prints_the_replicas_line_when_the_collective_legs_hang()
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_lines(r.stdout)[0]
     assert line["ulysses"]["value"] > 0 and line["ulysses_config3"]["value"] > 0
+
+
+def test_bench_refuses_options_it_cannot_honour():
+    # refused at argument parsing, before anything touches a GPU: no JSON line, a non-zero exit
+    for extra in (["--steps", "0"], ["--warmup", "-1"], ["--rehearse-both"]):
+        r = subprocess.run([sys.executable, BENCH] + extra, env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and _json_lines(r.stdout) == [], (extra, r.stderr[-2000:])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last_ones_outputs(tmp_path):
+    """A plain run is the headline only: exactly --steps timed steps, the line's headline fields, none of the --full legs;
+    --dump-outputs writes the updated latents and the last step's noise prediction as float32 .npy."""
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)], env=_env(),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = lines[0]
+    assert line["steps"] == 2 and line["step_ms"]["n"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "denoise-steps/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    for key in ("b_eff_1", "pipeline_default", "config3_step_1gpu", "attention", "vae_decode", "cpu_baseline"):
+        assert key not in line, key
+    lat, pred = np.load(out / "latents.npy"), np.load(out / "noise_pred.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 4992, 128) and np.isfinite(lat).all()
+    assert pred.dtype == np.float32 and pred.shape == (3, 4992, 128) and np.isfinite(pred).all()
+    assert np.abs(pred).max() > 0
