@@ -53,22 +53,19 @@ struct AttnParams {
     }
 };
 
-// attention_pipe.hip: software-pipelined self-attention (head_dim 64, no key bias).
-// Returns -1 when the shape is not taken (the caller then uses attention.hip's kernel).
+// The kernel instances behind ltxmi_attention_fwd_bf16, numbered as ltxmi_attention_kernel_id reports them (ABI: callers compare
+// ids, tests pin them); attn_select (attention.hip) alone chooses among them.  attention.hip's kernel at head_dim 64 (+ key bias,
+// + 64 query rows per wave) and 128 (+ key bias), the software-pipelined kernels of attention_pipe.hip (head_dim 64) and
+// attention_pipe128.hip (128), and attention_cross.hip's for short key sequences (K / V resident in LDS; head_dim 64).
+enum AttnKernel : int {
+    ATTN_DH64 = 0, ATTN_DH64_BIAS = 1, ATTN_DH64_QB2 = 2, ATTN_PIPE = 3,
+    ATTN_DH128 = 4, ATTN_DH128_BIAS = 5, ATTN_PIPE128 = 6, ATTN_CROSS = 7,
+};
+constexpr int ATTN_CROSS_MAX_KEYS = 256;
+
+// Launchers of the kernels in the other attention files: each runs the shape it is given (attn_select has chosen it)
 int launch_attn_pipe(AttnParams p, hipStream_t stream);
-// whether launch_attn_pipe takes this shape
-bool attn_pipe_takes(int B, int H, int Lq, int Lk, int head_dim, bool has_bias);
-// attention_pipe128.hip: the same for head_dim 128 (one 4-wave workgroup per CU, 512 registers per wave)
 int launch_attn_pipe128(AttnParams p, hipStream_t stream);
-bool attn_pipe128_takes(int B, int H, int Lq, int Lk, int head_dim, bool has_bias);
-// attention_cross.hip: short key sequences (<= 256 keys, head_dim 64; the T5 cross-attention): K / V resident in LDS
 int launch_attn_cross(AttnParams p, hipStream_t stream);
-bool attn_cross_takes(int B, int H, int Lq, int Lk, int head_dim);
-// both pipelined kernels address a (batch, head)'s K / V rows through buffer descriptors with 32-bit byte offsets: the rows
-// of all key tiles (+ the ring's run-ahead) must span less than 2 GiB
-inline bool attn_pipe_span_ok(int Lk, int64_t k_sl, int64_t v_sl, int head_dim) {
-    const int64_t k_span = ((int64_t)(Lk + 4 * 64) * k_sl + head_dim) * 2, v_span = ((int64_t)(Lk + 4 * 64) * v_sl + head_dim) * 2;
-    return k_span < (1ll << 31) && v_span < (1ll << 31);
-}
 
 }  // namespace ltxmi

@@ -449,6 +449,32 @@ static int launch(AttnParams p, hipStream_t stream) {
     return check_launch("ltxmi_attention_fwd_bf16");
 }
 
+// Which kernel runs a shape (sizes positive, head_dim 64 or 128): ltxmi_attention_fwd_bf16 launches it, ltxmi_attention_kernel_id
+// reports it.  Two shapes with the same id are computed with the same arithmetic per (batch, head, query row).
+static AttnKernel attn_select(int B, int H, int Lq, int Lk, int head_dim, bool has_bias, int64_t k_sl, int64_t v_sl) {
+    const int64_t wg256 = (int64_t)B * H * ((Lq + 255) / 256);      // workgroups of 256 query rows
+    // the pipelined kernels address a (batch, head)'s K / V rows through buffer descriptors with 32-bit byte offsets: the rows
+    // of all key tiles (+ the ring's run-ahead of 4 tiles) must span less than 2 GiB
+    const int64_t rows = (int64_t)Lk + 4 * 64;
+    const bool span_ok = (rows * k_sl + head_dim) * 2 < (1ll << 31) && (rows * v_sl + head_dim) * 2 < (1ll << 31);
+    if (head_dim == 128) {
+        // pipelined, one 256-row workgroup per CU: from about half a chip's worth of workgroups on, and with enough key tiles for
+        // the ring's prologue / drain to amortise (config 4's 512-key text cross-attention stays on the register-staged kernel)
+        if (!has_bias && wg256 >= 128 && Lk >= 1024 && span_ok) return ATTN_PIPE128;
+        return has_bias ? ATTN_DH128_BIAS : ATTN_DH128;
+    }
+    // short key sequences (the T5 cross-attention), with enough query rows that the one-time K / V load pays (every
+    // workgroup gets at least two iterations of 128 rows)
+    if (Lk <= ATTN_CROSS_MAX_KEYS && Lq >= 1024) return ATTN_CROSS;
+    // from 192 workgroups (of the chip's 512 slots) the pipelined kernel beats attention.hip's: measured +11 % at 240 and +20 %
+    // at 480 workgroups (B 3, N 4992 with 4 / 8 heads: what a rank sees in the Ulysses mode at P = 8 / 4)
+    if (!has_bias && wg256 >= 192 && span_ok) return ATTN_PIPE;
+    // 64 query rows per wave (two blocks sharing each K / V fragment) once there is enough work to fill the chip with 256-row
+    // workgroups; 32 otherwise (and always at head_dim 128: two blocks of accumulators do not fit at 2 waves per SIMD)
+    if (!has_bias && wg256 >= 512) return ATTN_DH64_QB2;
+    return has_bias ? ATTN_DH64_BIAS : ATTN_DH64;
+}
+
 }  // namespace ltxmi
 
 using namespace ltxmi;
@@ -486,8 +512,6 @@ extern "C" int ltxmi_attention_fwd_bf16(const ltxmi_attn_args* a, void* stream) 
     p.redo_count = a->redo_counter; p.force_exact = a->force_exact != 0;
     LTXMI_REQUIRE(a->o_segment_len >= 0 && a->o_stride_segment % 8 == 0, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_attention_fwd_bf16: bad output segment geometry");
-    const bool span_ok = attn_pipe_span_ok(a->Lk, a->k_stride_l, a->v_stride_l, a->head_dim);
-    const bool pipe_ok = span_ok && attn_pipe_takes(a->B, a->H, a->Lq, a->Lk, a->head_dim, a->key_bias != nullptr);
     if (a->q_rowsumsq || a->q_rstd) {
         LTXMI_REQUIRE(a->q_norm_weight && (((uintptr_t)a->q_norm_weight) & 15) == 0 &&
                           (a->q_rstd ? (((uintptr_t)a->q_rstd) & 3) == 0
@@ -501,47 +525,26 @@ extern "C" int ltxmi_attention_fwd_bf16(const ltxmi_attn_args* a, void* stream) 
                           LTXMI_ERR_INVALID_ARG, "ltxmi_attention_fwd_bf16: RoPE tables must be 16-byte aligned rows");
     }
     hipStream_t s = (hipStream_t)stream;
-    // 64 query rows per wave (two blocks sharing each K/V fragment) once there is enough work to
-    // fill the chip with 256-row workgroups; 32 rows per wave otherwise (and always at head_dim 128,
-    // where two blocks of accumulators do not fit the register file at 2 waves per SIMD)
-    const int64_t wg256 = (int64_t)a->B * a->H * ((a->Lq + 255) / 256);
-    if (a->head_dim == 64) {
-        // short key sequences (the T5 cross-attention): K / V resident in LDS, single-pass softmax (attention_cross.hip)
-        if (attn_cross_takes(a->B, a->H, a->Lq, a->Lk, a->head_dim)) return launch_attn_cross(p, s);
-        // large self-attention: the software-pipelined LDS-DMA kernel (attention_pipe.hip)
-        if (pipe_ok) {
-            const int rc = launch_attn_pipe(p, s);
-            if (rc != -1) return rc;
-        }
-        if (wg256 >= 512 && !a->key_bias) return launch<64, false, ATTN_QB_BIG>(p, s);
-        return a->key_bias ? launch<64, true, 1>(p, s) : launch<64, false, 1>(p, s);
+    switch (attn_select(a->B, a->H, a->Lq, a->Lk, a->head_dim, a->key_bias != nullptr, a->k_stride_l, a->v_stride_l)) {
+        case ATTN_DH64: return launch<64, false, 1>(p, s);
+        case ATTN_DH64_BIAS: return launch<64, true, 1>(p, s);
+        case ATTN_DH64_QB2: return launch<64, false, ATTN_QB_BIG>(p, s);
+        case ATTN_PIPE: return launch_attn_pipe(p, s);
+        case ATTN_DH128: return launch<128, false, 1>(p, s);
+        case ATTN_DH128_BIAS: return launch<128, true, 1>(p, s);
+        case ATTN_PIPE128: return launch_attn_pipe128(p, s);
+        case ATTN_CROSS: return launch_attn_cross(p, s);
     }
-    // head_dim 128, large self-attention: the one-wave-per-SIMD pipelined kernel (attention_pipe128.hip)
-    if (span_ok && attn_pipe128_takes(a->B, a->H, a->Lq, a->Lk, a->head_dim, a->key_bias != nullptr)) {
-        const int rc = launch_attn_pipe128(p, s);
-        if (rc != -1) return rc;
-    }
-    return a->key_bias ? launch<128, true, 1>(p, s) : launch<128, false, 1>(p, s);
 }
 
-// Which kernel instance ltxmi_attention_fwd_bf16 runs for a shape (mirrors the dispatch above, INCLUDING the 2 GiB span test
-// of the pipelined kernels, which depends on the key / value token strides).  Two shapes with the same id are computed with
-// the same arithmetic per (batch, head, query row): what ltxmi.Transformer3DModel checks before it runs a sub-batch of rows
-// and claims bit-identity with the full batch.
+// Which kernel instance ltxmi_attention_fwd_bf16 runs for a shape (attn_select, whose answer depends on the key / value token
+// strides through the pipelined kernels' 2 GiB span limit): what ltxmi.Transformer3DModel checks before it runs a sub-batch of
+// rows and claims bit-identity with the full batch.
 extern "C" int ltxmi_attention_kernel_id(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, int32_t has_key_bias,
                                          int64_t k_stride_l, int64_t v_stride_l) {
     if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || k_stride_l <= 0 || v_stride_l <= 0) return -1;
     if (head_dim != 64 && head_dim != 128) return -1;
-    const bool span_ok = attn_pipe_span_ok(Lk, k_stride_l, v_stride_l, head_dim);
-    if (head_dim == 128) {
-        if (span_ok && attn_pipe128_takes(B, H, Lq, Lk, head_dim, has_key_bias != 0)) return 6;
-        return has_key_bias ? 5 : 4;
-    }
-    if (attn_cross_takes(B, H, Lq, Lk, head_dim)) return 7;
-    if (span_ok && attn_pipe_takes(B, H, Lq, Lk, head_dim, has_key_bias != 0)) return 3;
-    const int64_t wg256 = (int64_t)B * H * ((Lq + 255) / 256);
-    if (wg256 >= 512 && !has_key_bias) return 2;
-    return has_key_bias ? 1 : 0;
+    return attn_select(B, H, Lq, Lk, head_dim, has_key_bias != 0, k_stride_l, v_stride_l);
 }
 
 extern "C" int ltxmi_attention_fuses_qnorm(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, int32_t has_key_bias) {

@@ -324,11 +324,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
 
 }  // namespace cross
 
-// Shapes this kernel takes: head_dim 64, at most 256 keys, and enough query rows that the one-time K / V load pays (every
-// workgroup gets at least two iterations of 128 rows).
-bool attn_cross_takes(int B, int H, int Lq, int Lk, int head_dim) {
-    return head_dim == 64 && Lk >= 1 && Lk <= cross::MAX_TILES * cross::KV_TILE && Lq >= 1024;
-}
+static_assert(cross::MAX_TILES * cross::KV_TILE == ATTN_CROSS_MAX_KEYS, "attn_select hands this kernel up to ATTN_CROSS_MAX_KEYS keys");
 
 int launch_attn_cross(AttnParams p, hipStream_t stream) {
     const int n_cu = device_cu_count("ltxmi_attention_fwd_bf16");

@@ -565,15 +565,7 @@ extern "C" int ltxmi_debug_set_attn_stamps(void* buf) {
 #define LTXMI_ATTN_PIPE_OCC 2
 #endif
 
-bool attn_pipe_takes(int B, int H, int Lq, int Lk, int head_dim, bool has_bias) {
-    // from 192 workgroups of 256 rows (of the chip's 512 slots) this kernel beats attention.hip's: measured +11 % at 240
-    // and +20 % at 480 workgroups (B 3, N 4992 with 4 / 8 heads: what a rank sees in the Ulysses mode at P = 8 / 4)
-    return head_dim == 64 && !has_bias && (int64_t)B * H * ((Lq + 255) / 256) >= 192 && Lk > 0;
-}
-
 int launch_attn_pipe(AttnParams p, hipStream_t stream) {
-    // the buffer descriptors address a (batch, head)'s K / V rows with 32-bit byte offsets
-    if (!attn_pipe_span_ok(p.Lk, p.k_sl, p.v_sl, pipe::DH)) return -1;
     const bool qscaled = p.q_on_load();
     auto kern = p.force_exact ? (qscaled ? pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, true, true> : pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, false, true>)
                               : (qscaled ? pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, true, false> : pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, false, false>);

@@ -492,15 +492,7 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
 
 }  // namespace pipe128
 
-bool attn_pipe128_takes(int B, int H, int Lq, int Lk, int head_dim, bool has_bias) {
-    // one 256-row workgroup per CU: from about half a chip's worth of workgroups on, and with enough key tiles for the
-    // ring's prologue / drain to amortise (the 512-key text cross-attention of config 4 stays on the register-staged kernel)
-    return head_dim == 128 && !has_bias && (int64_t)B * H * ((Lq + 255) / 256) >= 128 && Lk >= 1024;
-}
-
 int launch_attn_pipe128(AttnParams p, hipStream_t stream) {
-    // the buffer descriptors address a (batch, head)'s K / V rows with 32-bit byte offsets
-    if (!attn_pipe_span_ok(p.Lk, p.k_sl, p.v_sl, pipe128::DH)) return -1;
     auto kern = pipe128::attn_pipe128_kernel;
     static unsigned long long lds_done = 0;
     if (const int rc = reserve_lds((const void*)kern, pipe128::SMEM + 16, &lds_done, "ltxmi_attention_fwd_bf16")) return rc;

@@ -89,10 +89,22 @@ int check_launch(const char* what);
 //   device_cu_count: CUs of the current device (cached per device), <= 0 on failure.
 int reserve_lds(const void* kernel, int bytes, unsigned long long* done, const char* what);
 int device_cu_count(const char* what);
-// conv_direct.hip: direct 3x3x3 convolution; -1 = shape not taken (use the implicit GEMM)
-int launch_conv3d_direct(const ltxmi_conv3d_args* a, hipStream_t stream);
-int64_t conv3d_direct_workspace_bytes(const ltxmi_conv3d_args* a);   // conv_direct.hip: the workspace a call would like (0: none)
-bool conv3d_direct_fuses_post_norm(const ltxmi_conv3d_args* a);     // conv_direct.hip: would this call apply post_norm in its epilogue
+// ltxmi_conv3d_ndhwc_bf16 (conv_direct.hip): how one call runs, worked out once from its arguments by conv3d_plan; the launch acts
+// on it and ltxmi_conv3d_workspace_bytes / ltxmi_conv3d_fuses_post_norm return its fields.  CONV_REFUSED: algo asks for the
+// direct convolution, which does not take the shape.
+enum ConvRoute : int { CONV_GEMM128, CONV_GEMM256, CONV_DIRECT8, CONV_DIRECT4, CONV_REFUSED };
+struct ConvPlan {
+    int kt, sT, sHW, tpad;              // kernel frames, time / space strides, frames of padding in front
+    int oT, oH, oW; int64_t M;          // output grid, M = B oT oH oW positions
+    ConvRoute route;                    // the implicit GEMM (gemm.hip) with 128- / 256-wide tiles, the eight- / four-wave direct form
+    int epi;                            // 0 plain, 1 + add, 2 depth-to-space; four-wave form also 3 .. 5 = the same + post_norm,
+                                        // 6 = fp32 partial sums of a channel split (the finalising pass applies the epilogue)
+    int swap, ksplit, tiles_t, tiles_8, tiles_16, tiles_n;    // direct forms: see conv3d_plan
+    int64_t grid, split_bytes;          // workgroups of ONE channel range; workspace the split needs (0: no split pays)
+    bool fuses_post_norm;               // post_norm = 1 would be applied in the epilogue
+};
+int conv3d_gemm_tile(int64_t M, int Cout);     // gemm.hip: the implicit GEMM's tile (128 or 256) for M positions x Cout
+int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream);
 
 }  // namespace ltxmi
 

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
 // The stream and the tables are the kernel above with these constants.  Round 4 added, here only: one epilogue code path for
 // seven forms (0 plain, 1 + add, 2 depth-to-space + residual, 3 PixelNorm -> AdaLN -> SiLU of the result, 4 / 5 = 1 / 2 with that
 // as a SECOND output, 6 fp32 partial sums of a range of input channels), tiles whose 16-position rows run along H instead of W,
-// and the split over the input channels (ConvDirectP::swap_hw / ksplit, conv3d_direct_plan, conv_split_finalize_kernel below).
+// and the split over the input channels (ConvDirectP::swap_hw / ksplit, conv3d_plan, conv_split_finalize_kernel below).
 namespace v3 {
 constexpr int TT = 2, TY = 8, TX = 16;
 constexpr int HT = TT + 2, HY = TY + 2, HX = TX + 2;
@@ -1080,26 +1080,35 @@ static bool conv3d_direct_four_wave_form(const ltxmi_conv3d_args* a, int64_t gri
 // wide, short layers (Cin >= 1024: the partial sums are Cin / (4 ksplit) times smaller than the halo traffic they replace) whose
 // tiles do not fill the chip: 1024 -> 1024 at 13 x 16 x 24 positions is 224 tiles of which 70 % of the positions exist (W = 24
 // is 1.5 tiles); swapped it is 168 tiles at 93 %, and three channel ranges make 504 workgroups for the 512 slots.
-struct ConvPlan {
-    bool four_wave; int swap, ksplit;
-    int tiles_t, tiles_8, tiles_16, tiles_n;      // tiles along t, the 8-row direction, the 16-position direction, 128-channel blocks
-    int64_t grid;                                 // workgroups of ONE channel range
-    int64_t workspace_bytes;                      // ksplit > 1: [ksplit][B T H W][Cout] fp32
-};
-static ConvPlan conv3d_direct_plan(const ltxmi_conv3d_args* a, bool have_workspace) {
-    ConvPlan pl;
+static ConvPlan conv3d_plan(const ltxmi_conv3d_args* a) {      // a != NULL, sizes positive; algo honoured as given
+    ConvPlan pl = {};
+    // output grid: nn.Conv3d arithmetic on the padded input (time padded by tpad frames in front, and by one replicated frame
+    // behind when not causal; space padded by 1): floor((L + pad - 3) / s) + 1
+    pl.sT = a->stride_t > 0 ? a->stride_t : 1; pl.sHW = a->stride_hw > 0 ? a->stride_hw : 1;
+    pl.kt = a->kernel_t > 0 ? a->kernel_t : 3;       // 1: a 3x3 nn.Conv2d applied to every frame
+    pl.tpad = pl.kt == 1 ? 0 : (a->tpad > 0 ? a->tpad : (a->causal ? 2 : 1));
+    const int tpad_back = (pl.kt == 1 || a->tpad > 0 || a->causal) ? 0 : 1;
+    pl.oT = a->out_T > 0 ? a->out_T : (a->T + pl.tpad + tpad_back - pl.kt) / pl.sT + 1;
+    pl.oH = (a->H + 2 - 3) / pl.sHW + 1; pl.oW = (a->W + 2 - 3) / pl.sHW + 1;
+    pl.M = (int64_t)a->B * pl.oT * pl.oH * pl.oW;
+    pl.epi = a->d2s ? 2 : (a->add ? 1 : 0);
+    pl.ksplit = 1;
+    const ConvRoute gemm = conv3d_gemm_tile(pl.M, a->Cout) == 256 ? CONV_GEMM256 : CONV_GEMM128;
+    if (a->algo == 1 || !conv3d_direct_takes(a)) {
+        pl.route = a->algo >= 2 ? CONV_REFUSED : gemm;
+        return pl;
+    }
     pl.tiles_t = (a->T + CD_TT - 1) / CD_TT; pl.tiles_n = (a->Cout + 127) / 128;
     const int64_t per = (int64_t)a->B * pl.tiles_t * pl.tiles_n;
     const int64_t g_n = per * ((a->H + 7) / 8) * ((a->W + 15) / 16), g_s = per * ((a->W + 7) / 8) * ((a->H + 15) / 16);
-    pl.swap = 0; pl.ksplit = 1; pl.workspace_bytes = 0;
-    pl.four_wave = conv3d_direct_four_wave_form(a, g_n);
+    bool four_wave = conv3d_direct_four_wave_form(a, g_n);
     const double positions = (double)a->B * pl.tiles_t * CD_TT * a->H * a->W * pl.tiles_n;       // (x 128 channels each, t rounded up)
     auto eff4 = [&](int64_t g, int S) {           // useful share of the tiles x fill of the last round of 512 slots - the split's price
         const double rounds = (double)g * S / 512.0;
         return positions / ((double)g * 256.0) * rounds / (double)(int64_t)(rounds + 0.999999) - 0.03 * (S - 1);
     };
-    const double eff_now = pl.four_wave ? eff4(g_n, 1)
-                                        : positions / ((double)g_n * 256.0) * ((double)g_n / 256.0) / (double)((g_n + 255) / 256) * 0.93;
+    const double eff_now = four_wave ? eff4(g_n, 1)
+                                     : positions / ((double)g_n * 256.0) * ((double)g_n / 256.0) / (double)((g_n + 255) / 256) * 0.93;
     // The channel split: the product's own choice (algo 0 / 2 / 3), output rows the finalising pass takes (512 or n x 1024
     // channels).  Cin >= 1024: wherever it buys more than 5 % of the launch at 3 % per extra range.  512 <= Cin < 1024 (the partial
     // sums cost twice as much per FLOP): two ranges only, and only for a call that asks for a norm the unsplit form could not
@@ -1119,53 +1128,51 @@ static ConvPlan conv3d_direct_plan(const ltxmi_conv3d_args* a, bool have_workspa
             if (g * S < (1ll << 31) && e > best_eff) { best = S; best_eff = e; }
         }
         if (best > 1) {
-            pl.workspace_bytes = (int64_t)best * a->B * a->T * a->H * a->W * a->Cout * 4;
-            if (have_workspace && a->workspace && a->workspace_bytes >= pl.workspace_bytes && (((uintptr_t)a->workspace) & 15) == 0) {
-                pl.ksplit = best; pl.four_wave = true; pl.swap = g_s < g_n;
+            pl.split_bytes = (int64_t)best * a->B * a->T * a->H * a->W * a->Cout * 4;
+            if (a->workspace && a->workspace_bytes >= pl.split_bytes && (((uintptr_t)a->workspace) & 15) == 0) {
+                pl.ksplit = best; four_wave = true; pl.swap = g_s < g_n;
             }
         }
     }
-    if (pl.ksplit == 1 && pl.four_wave && (g_s + 511) / 512 < (g_n + 511) / 512) pl.swap = 1;    // fewer rounds of the chip
+    if (pl.ksplit == 1 && four_wave && (g_s + 511) / 512 < (g_n + 511) / 512) pl.swap = 1;    // fewer rounds of the chip
     pl.tiles_8 = pl.swap ? (a->W + 7) / 8 : (a->H + 7) / 8;
     pl.tiles_16 = pl.swap ? (a->H + 15) / 16 : (a->W + 15) / 16;
     pl.grid = per * pl.tiles_8 * pl.tiles_16;
+    // post_norm rides along where a wave holds every channel of its output positions: ONE 128-channel block of the four-wave
+    // form (plain store; with `add` only as the second output y_norm beside the raw y), or its depth-to-space store to 128
+    // channels (second output only: a 128-column block is one (p1 p2 p3)) -- and on every call split over its input channels
+    // (the finalising pass holds whole rows).  Without y_norm the activated result is the only output: the plain store only.
+    if (a->y_norm || !(a->add || a->d2s)) {
+        pl.fuses_post_norm = pl.ksplit > 1 ||
+                             (four_wave && (a->y_norm ? (a->d2s && a->Cout == 1024) || (!a->d2s && a->add && a->Cout == 128)
+                                                      : a->Cout == 128));
+    }
+    if (four_wave) {
+        pl.route = CONV_DIRECT4;
+        pl.epi = pl.ksplit > 1 ? 6 : pl.epi + (a->post_norm && pl.fuses_post_norm ? 3 : 0);
+    } else if (pl.grid >= (1ll << 31) || (pl.grid < 128 && a->algo < 2)) {
+        // one eight-wave workgroup per CU is resident: below ~half the CUs the implicit GEMM's smaller tiles fill the chip
+        // better (algo >= 2 asks for the direct convolution whatever the grid)
+        pl.route = a->algo >= 2 ? CONV_REFUSED : gemm;
+    } else {
+        pl.route = CONV_DIRECT8;
+    }
     return pl;
 }
-int64_t conv3d_direct_workspace_bytes(const ltxmi_conv3d_args* a) {
-    if (a->algo == 1 || !conv3d_direct_takes(a)) return 0;
-    return conv3d_direct_plan(a, false).workspace_bytes;
-}
-// ltxmi_conv3d_fuses_post_norm: the four-wave form where a wave holds every channel of its output positions -- ONE 128-channel
-// block (plain store; with `add` only as the second output y_norm beside the raw y), or the depth-to-space store to 128 channels
-// (second output only: a 128-column block is one (p1 p2 p3)) -- and every call that runs split over its input channels (the
-// finalising pass holds whole rows)
-bool conv3d_direct_fuses_post_norm(const ltxmi_conv3d_args* a) {
-    if (a->algo == 1 || !conv3d_direct_takes(a)) return false;
-    if (!a->y_norm && (a->add || a->d2s)) return false;      // the activated result as the ONLY output: the plain store only
-    const ConvPlan pl = conv3d_direct_plan(a, true);
-    if (pl.ksplit > 1) return true;
-    if (!pl.four_wave) return false;
-    if (a->y_norm) return (a->d2s && a->Cout == 1024) || (!a->d2s && a->add && a->Cout == 128);
-    return a->Cout == 128 && !a->d2s && !a->add;
-}
 
-// Returns -1 when the shape is not one this kernel takes (the caller then uses the implicit GEMM).
-int launch_conv3d_direct(const ltxmi_conv3d_args* a, hipStream_t stream) {
-    if (!conv3d_direct_takes(a)) return -1;
-    const ConvPlan pl = conv3d_direct_plan(a, true);
+static int launch_conv3d_direct(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream) {
     ConvDirectP p;
     p.x = (const uint16_t*)a->x; p.w = (const uint16_t*)a->w; p.bias = (const uint16_t*)a->bias;
     p.y = (uint16_t*)a->y; p.add = (const uint16_t*)a->add;
     p.res = a->d2s ? (const uint16_t*)a->residual : nullptr; p.res_ch = a->res_channels;
     p.B = a->B; p.T = a->T; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout;
-    p.tpad = a->causal ? 2 : 1; p.pad_replicate = a->pad_replicate; p.tzero = a->time_pad_zeros ? 1 : 0;
+    p.tpad = pl.tpad; p.pad_replicate = a->pad_replicate; p.tzero = a->time_pad_zeros ? 1 : 0;
     p.tiles_t = pl.tiles_t; p.tiles_y = pl.tiles_8; p.tiles_x = pl.tiles_16; p.tiles_n = pl.tiles_n;
     p.swap_hw = pl.swap; p.ksplit = pl.ksplit; p.part = (float*)a->workspace;
     const int64_t grid = pl.grid * pl.ksplit;
     p.post_scale = a->post_scale; p.post_shift = a->post_shift; p.post_eps = a->post_eps;
     p.y2 = (uint16_t*)a->y_norm;
-    if (a->post_norm && !conv3d_direct_fuses_post_norm(a)) return -1;
-    if (pl.four_wave) {
+    if (pl.route == CONV_DIRECT4) {
 #define LTXMI_CDV3_LAUNCH(E)                                                                                   \
         {                                                                                                      \
             static unsigned long long lds_done = 0;                                                            \
@@ -1175,7 +1182,7 @@ int launch_conv3d_direct(const ltxmi_conv3d_args* a, hipStream_t stream) {
             hipLaunchKernelGGL(v3::conv3d_direct_v3_kernel<E>, dim3((unsigned)grid), dim3(256), v3::SMEM,      \
                                stream, p);                                                                     \
         }
-        if (pl.ksplit > 1) {
+        if (pl.epi == 6) {                  // the channel split, then the finalising pass
             LTXMI_CDV3_LAUNCH(6)
             if (const int rc_ = check_launch("ltxmi_conv3d_ndhwc_bf16")) return rc_;
             ConvFinalizeP f;
@@ -1196,19 +1203,17 @@ int launch_conv3d_direct(const ltxmi_conv3d_args* a, hipStream_t stream) {
             }
             return check_launch("ltxmi_conv3d_ndhwc_bf16");
         }
-        if (a->d2s && a->post_norm) LTXMI_CDV3_LAUNCH(5)
-        else if (a->add && a->post_norm) LTXMI_CDV3_LAUNCH(4)
-        else if (a->d2s) LTXMI_CDV3_LAUNCH(2)
-        else if (a->add) LTXMI_CDV3_LAUNCH(1)
-        else if (a->post_norm) LTXMI_CDV3_LAUNCH(3)
-        else LTXMI_CDV3_LAUNCH(0)
+        switch (pl.epi) {
+            case 0: LTXMI_CDV3_LAUNCH(0) break;
+            case 1: LTXMI_CDV3_LAUNCH(1) break;
+            case 2: LTXMI_CDV3_LAUNCH(2) break;
+            case 3: LTXMI_CDV3_LAUNCH(3) break;
+            case 4: LTXMI_CDV3_LAUNCH(4) break;
+            default: LTXMI_CDV3_LAUNCH(5) break;
+        }
 #undef LTXMI_CDV3_LAUNCH
         return check_launch("ltxmi_conv3d_ndhwc_bf16");
     }
-    // one workgroup per CU is resident: below ~half the CUs the implicit GEMM's smaller tiles fill the chip better
-    // (algo >= 2 asks for the direct convolution whatever the grid)
-    constexpr int min_grid = 128;
-    if (grid >= (1ll << 31) || (grid < min_grid && a->algo < 2)) return -1;
 #define LTXMI_CD_LAUNCH(E)                                                                                     \
     {                                                                                                          \
         static unsigned long long lds_done = 0;                                                                \
@@ -1217,11 +1222,71 @@ int launch_conv3d_direct(const ltxmi_conv3d_args* a, hipStream_t stream) {
             return rc_;                                                                                        \
         hipLaunchKernelGGL(conv3d_direct_kernel<E>, dim3((unsigned)grid), dim3(512), CD_SMEM, stream, p);      \
     }
-    if (a->d2s) LTXMI_CD_LAUNCH(2)
-    else if (a->add) LTXMI_CD_LAUNCH(1)
+    if (pl.epi == 2) LTXMI_CD_LAUNCH(2)
+    else if (pl.epi == 1) LTXMI_CD_LAUNCH(1)
     else LTXMI_CD_LAUNCH(0)
 #undef LTXMI_CD_LAUNCH
     return check_launch("ltxmi_conv3d_ndhwc_bf16");
 }
 
 }  // namespace ltxmi
+
+using namespace ltxmi;
+
+// the two queries: fields of the plan of the arguments as given (0 without a bias -- the direct convolution needs one)
+static bool conv3d_plannable(const ltxmi_conv3d_args* a) {
+    return a != nullptr && a->bias != nullptr && a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0;
+}
+extern "C" int ltxmi_conv3d_fuses_post_norm(const ltxmi_conv3d_args* a) { return conv3d_plannable(a) && conv3d_plan(a).fuses_post_norm; }
+extern "C" int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* a) { return conv3d_plannable(a) ? conv3d_plan(a).split_bytes : 0; }
+
+extern "C" int ltxmi_conv3d_ndhwc_bf16(const ltxmi_conv3d_args* a, void* stream) {
+    LTXMI_REQUIRE(a && a->x && a->w && a->y, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: NULL argument");
+    LTXMI_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_conv3d_ndhwc_bf16: non-positive shape");
+    const ConvPlan pl = conv3d_plan(a);
+    LTXMI_REQUIRE(a->Cin % 64 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cin=%d must be a multiple of 64", a->Cin);
+    LTXMI_REQUIRE(a->Cout % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cout=%d must be a multiple of 8", a->Cout);
+    LTXMI_REQUIRE((pl.sT == 1 || pl.sT == 2) && (pl.sHW == 1 || pl.sHW == 2), LTXMI_ERR_UNSUPPORTED,
+                  "ltxmi_conv3d_ndhwc_bf16: strides must be 1 or 2");
+    LTXMI_REQUIRE(pl.kt == 3 || (pl.kt == 1 && pl.sT == 1 && a->tpad == 0 && a->out_T == 0), LTXMI_ERR_UNSUPPORTED,
+                  "ltxmi_conv3d_ndhwc_bf16: kernel_t must be 3, or 1 without time stride/padding");
+    LTXMI_REQUIRE(!(a->d2s && (pl.sT != 1 || pl.sHW != 1 || pl.oT != a->T)), LTXMI_ERR_UNSUPPORTED,
+                  "ltxmi_conv3d_ndhwc_bf16: depth-to-space store needs a stride-1, same-size convolution");
+    LTXMI_REQUIRE(pl.M < (1ll << 31) && (int64_t)a->B * (2 * a->T) * (2 * a->H) * (2 * a->W) < (1ll << 31),
+                  LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: too many positions");
+    if (a->d2s) {
+        LTXMI_REQUIRE(a->Cout % 32 == 0, LTXMI_ERR_UNSUPPORTED,
+                      "ltxmi_conv3d_ndhwc_bf16: depth-to-space needs Cout %% 32 == 0 (got %d)", a->Cout);
+        if (a->residual)
+            LTXMI_REQUIRE(a->res_channels > 0 && a->res_channels % 8 == 0, LTXMI_ERR_INVALID_ARG,
+                          "ltxmi_conv3d_ndhwc_bf16: bad residual channel count %d", a->res_channels);
+    }
+    LTXMI_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->w) & 15) == 0 && (((uintptr_t)a->y | (uintptr_t)a->bias) & 7) == 0,
+                  LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: misaligned pointer");
+    LTXMI_REQUIRE(a->algo >= 0 && a->algo <= 4, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: algo %d not in {0 .. 4}", a->algo);
+    LTXMI_REQUIRE(a->workspace_bytes >= 0 && (a->workspace != nullptr || a->workspace_bytes == 0), LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_conv3d_ndhwc_bf16: workspace_bytes without a workspace");
+    if (a->post_norm) {
+        LTXMI_REQUIRE(a->post_norm == 1 && (a->post_scale != nullptr) == (a->post_shift != nullptr) && a->post_eps >= 0.f,
+                      LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: post_norm must be 0 or 1, post_scale / post_shift both given or both NULL");
+        LTXMI_REQUIRE((((uintptr_t)a->post_scale | (uintptr_t)a->post_shift) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
+                      "ltxmi_conv3d_ndhwc_bf16: misaligned post_scale / post_shift");
+        LTXMI_REQUIRE(((uintptr_t)a->y_norm & 15) == 0 && a->y_norm != a->y, LTXMI_ERR_INVALID_ARG,
+                      "ltxmi_conv3d_ndhwc_bf16: y_norm must be 16-byte aligned and distinct from y");
+        LTXMI_REQUIRE(pl.fuses_post_norm, LTXMI_ERR_UNSUPPORTED,
+                      "ltxmi_conv3d_ndhwc_bf16: post_norm is applied by the four-wave direct convolution where a wave holds all "
+                      "channels of a position (ask ltxmi_conv3d_fuses_post_norm first)");
+    } else {
+        LTXMI_REQUIRE(a->y_norm == nullptr, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: y_norm without post_norm");
+    }
+    switch (pl.route) {
+        case CONV_DIRECT4:
+        case CONV_DIRECT8: return launch_conv3d_direct(a, pl, (hipStream_t)stream);
+        case CONV_GEMM128:
+        case CONV_GEMM256: return launch_conv3d_gemm(a, pl, (hipStream_t)stream);
+        case CONV_REFUSED: break;
+    }
+    set_error("ltxmi_conv3d_ndhwc_bf16: algo = %d (direct convolution) does not take this shape", a->algo);
+    return LTXMI_ERR_UNSUPPORTED;
+}

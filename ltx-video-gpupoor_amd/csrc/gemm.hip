@@ -949,6 +949,38 @@ static const uint16_t* zero_page_ptr() {
     return (const uint16_t*)d;
 }
 
+// the implicit-GEMM convolution: 256 x 256 tiles (8 waves) when they still fill the chip, else 128 x 128
+int conv3d_gemm_tile(int64_t M, int Cout) {
+    const long t256 = (long)((M + 255) / 256) * ((Cout + 255) / 256);
+    return Cout >= 256 && t256 >= 384 ? 256 : 128;
+}
+
+int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream) {
+    GemmParams p;
+    p.A = (const uint16_t*)a->x; p.lda = a->Cin;
+    p.W = (const uint16_t*)a->w; p.ldw = 9ll * pl.kt * a->Cin;
+    p.bias = a->bias ? (const uint16_t*)a->bias : zero_page_ptr();
+    p.bias_stride = a->bias ? 1 : 0;
+    LTXMI_REQUIRE(p.bias, LTXMI_ERR_LAUNCH, "ltxmi_conv3d_ndhwc_bf16: cannot resolve the zero page");
+    p.C = (uint16_t*)a->y; p.ldc = a->Cout;
+    p.M = (int)pl.M; p.N = a->Cout; p.K = 9 * pl.kt * a->Cin;
+    p.R = nullptr; p.ldr = 0; p.gate_table = nullptr; p.gate_temb = nullptr; p.gate_ld = 0; p.rows_per_group = 1;
+    p.sumsq = nullptr; p.sumsq_cols = 0; p.sumsq_ld = 0; p.a_kblk = 0; p.a_kblk_stride = 0;
+    p.tiles_m = p.tiles_n = 0;
+    p.cB = a->B; p.cT = a->T; p.cH = a->H; p.cW = a->W; p.cCin = a->Cin;
+    p.oT = pl.oT; p.oH = pl.oH; p.oW = pl.oW; p.sT = pl.sT; p.sHW = pl.sHW;
+    p.tpad = pl.tpad;
+    p.tzero = a->time_pad_zeros ? 1 : 0;
+    p.pad_replicate = a->pad_replicate;
+    p.res = a->d2s ? (const uint16_t*)a->residual : nullptr;
+    p.res_ch = a->res_channels;
+    LTXMI_REQUIRE(!(a->d2s && a->add), LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: `add` is for the plain store only");
+    if (a->add) { p.R = (const uint16_t*)a->add; p.ldr = a->Cout; }
+    const int epi = pl.epi == 2 ? EPI_D2S : (pl.epi == 1 ? EPI_RESIDUAL : LTXMI_EPI_NONE);
+    if (pl.route == CONV_GEMM256) return launch_tile<256, 256, 2, 4, 1>(p, epi, stream, "ltxmi_conv3d_ndhwc_bf16");
+    return launch_tile<128, 128, 2, 2, 1>(p, epi, stream, "ltxmi_conv3d_ndhwc_bf16");
+}
+
 }  // namespace ltxmi
 
 using namespace ltxmi;
@@ -1042,94 +1074,3 @@ extern "C" int ltxmi_debug_set_gemm_stamps(void* buf) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(ltxmi::g_gemm_stamps), &b, sizeof(b));
 }
 #endif
-
-extern "C" int ltxmi_conv3d_fuses_post_norm(const ltxmi_conv3d_args* a) {
-    return a != nullptr && a->bias != nullptr && a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0 &&
-                   conv3d_direct_fuses_post_norm(a) ? 1 : 0;
-}
-
-extern "C" int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* a) {
-    return a != nullptr && a->bias != nullptr && a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0
-               ? conv3d_direct_workspace_bytes(a) : 0;
-}
-
-extern "C" int ltxmi_conv3d_ndhwc_bf16(const ltxmi_conv3d_args* a, void* stream) {
-    LTXMI_REQUIRE(a && a->x && a->w && a->y, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: NULL argument");
-    LTXMI_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, LTXMI_ERR_INVALID_ARG,
-                  "ltxmi_conv3d_ndhwc_bf16: non-positive shape");
-    LTXMI_REQUIRE(a->Cin % 64 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cin=%d must be a multiple of 64", a->Cin);
-    LTXMI_REQUIRE(a->Cout % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cout=%d must be a multiple of 8", a->Cout);
-    const int sT = a->stride_t > 0 ? a->stride_t : 1, sHW = a->stride_hw > 0 ? a->stride_hw : 1;
-    LTXMI_REQUIRE((sT == 1 || sT == 2) && (sHW == 1 || sHW == 2), LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: strides must be 1 or 2");
-    // output grid: nn.Conv3d arithmetic on the padded input (time padded by tpad frames in front, and by
-    // one replicated frame behind when not causal; space padded by 1): floor((L + pad - 3) / s) + 1
-    const int kt = a->kernel_t > 0 ? a->kernel_t : 3;       // 1: a 3x3 nn.Conv2d applied to every frame
-    LTXMI_REQUIRE(kt == 3 || (kt == 1 && sT == 1 && a->tpad == 0 && a->out_T == 0), LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: kernel_t must be 3, or 1 without time stride/padding");
-    const int tpad_front = kt == 1 ? 0 : (a->tpad > 0 ? a->tpad : (a->causal ? 2 : 1));
-    const int tpad_back = (kt == 1 || a->tpad > 0 || a->causal) ? 0 : 1;
-    const int oT = a->out_T > 0 ? a->out_T : (a->T + tpad_front + tpad_back - kt) / sT + 1;
-    const int oH = (a->H + 2 - 3) / sHW + 1, oW = (a->W + 2 - 3) / sHW + 1;
-    LTXMI_REQUIRE(!(a->d2s && (sT != 1 || sHW != 1 || oT != a->T)), LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: depth-to-space store needs a stride-1, same-size convolution");
-    const int64_t M = (int64_t)a->B * oT * oH * oW;
-    LTXMI_REQUIRE(M < (1ll << 31) && (int64_t)a->B * (2 * a->T) * (2 * a->H) * (2 * a->W) < (1ll << 31),
-                  LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: too many positions");
-    if (a->d2s) {
-        LTXMI_REQUIRE(a->Cout % 32 == 0, LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: depth-to-space needs Cout %% 32 == 0 (got %d)", a->Cout);
-        if (a->residual)
-            LTXMI_REQUIRE(a->res_channels > 0 && a->res_channels % 8 == 0, LTXMI_ERR_INVALID_ARG,
-                          "ltxmi_conv3d_ndhwc_bf16: bad residual channel count %d", a->res_channels);
-    }
-    LTXMI_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->w) & 15) == 0 && (((uintptr_t)a->y | (uintptr_t)a->bias) & 7) == 0,
-                  LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: misaligned pointer");
-    LTXMI_REQUIRE(a->algo >= 0 && a->algo <= 4, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: algo %d not in {0 .. 4}", a->algo);
-    LTXMI_REQUIRE(a->workspace_bytes >= 0 && (a->workspace != nullptr || a->workspace_bytes == 0), LTXMI_ERR_INVALID_ARG,
-                  "ltxmi_conv3d_ndhwc_bf16: workspace_bytes without a workspace");
-    if (a->post_norm) {
-        LTXMI_REQUIRE(a->post_norm == 1 && (a->post_scale != nullptr) == (a->post_shift != nullptr) && a->post_eps >= 0.f,
-                      LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: post_norm must be 0 or 1, post_scale / post_shift both given or both NULL");
-        LTXMI_REQUIRE((((uintptr_t)a->post_scale | (uintptr_t)a->post_shift) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: misaligned post_scale / post_shift");
-        LTXMI_REQUIRE(((uintptr_t)a->y_norm & 15) == 0 && a->y_norm != a->y, LTXMI_ERR_INVALID_ARG,
-                      "ltxmi_conv3d_ndhwc_bf16: y_norm must be 16-byte aligned and distinct from y");
-        LTXMI_REQUIRE(conv3d_direct_fuses_post_norm(a), LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: post_norm is applied by the four-wave direct convolution where a wave holds all "
-                      "channels of a position (ask ltxmi_conv3d_fuses_post_norm first)");
-    } else {
-        LTXMI_REQUIRE(a->y_norm == nullptr, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: y_norm without post_norm");
-    }
-    if (a->algo != 1) {
-        const int rc = launch_conv3d_direct(a, (hipStream_t)stream);      // narrow stride-1 layers: direct convolution
-        if (rc >= 0) return rc;
-        LTXMI_REQUIRE(a->algo < 2, LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: algo = %d (direct convolution) does not take this shape", a->algo);
-    }
-    GemmParams p;
-    p.A = (const uint16_t*)a->x; p.lda = a->Cin;
-    p.W = (const uint16_t*)a->w; p.ldw = 9ll * kt * a->Cin;
-    p.bias = a->bias ? (const uint16_t*)a->bias : zero_page_ptr();
-    p.bias_stride = a->bias ? 1 : 0;
-    LTXMI_REQUIRE(p.bias, LTXMI_ERR_LAUNCH, "ltxmi_conv3d_ndhwc_bf16: cannot resolve the zero page");
-    p.C = (uint16_t*)a->y; p.ldc = a->Cout;
-    p.M = (int)M; p.N = a->Cout; p.K = 9 * kt * a->Cin;
-    p.R = nullptr; p.ldr = 0; p.gate_table = nullptr; p.gate_temb = nullptr; p.gate_ld = 0; p.rows_per_group = 1;
-    p.sumsq = nullptr; p.sumsq_cols = 0; p.sumsq_ld = 0; p.a_kblk = 0; p.a_kblk_stride = 0;
-    p.tiles_m = p.tiles_n = 0;
-    p.cB = a->B; p.cT = a->T; p.cH = a->H; p.cW = a->W; p.cCin = a->Cin;
-    p.oT = oT; p.oH = oH; p.oW = oW; p.sT = sT; p.sHW = sHW;
-    p.tpad = tpad_front;
-    p.tzero = a->time_pad_zeros ? 1 : 0;
-    p.pad_replicate = a->pad_replicate;
-    p.res = a->d2s ? (const uint16_t*)a->residual : nullptr;
-    p.res_ch = a->res_channels;
-    hipStream_t s = (hipStream_t)stream;
-    LTXMI_REQUIRE(!(a->d2s && a->add), LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: `add` is for the plain store only");
-    if (a->add) { p.R = (const uint16_t*)a->add; p.ldr = a->Cout; }
-    const int epi = a->d2s ? EPI_D2S : (a->add ? EPI_RESIDUAL : LTXMI_EPI_NONE);
-    const long t256 = (long)((M + 255) / 256) * ((a->Cout + 255) / 256);
-    if (a->Cout >= 256 && t256 >= 384) return launch_tile<256, 256, 2, 4, 1>(p, epi, s, "ltxmi_conv3d_ndhwc_bf16");
-    return launch_tile<128, 128, 2, 2, 1>(p, epi, s, "ltxmi_conv3d_ndhwc_bf16");
-}

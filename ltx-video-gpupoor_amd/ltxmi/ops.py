@@ -432,7 +432,6 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
         if not add.is_contiguous() or add.shape != (B, oT, oH, oW, Cout):
             raise ValueError("ltxmi.conv3d: `add` must be a contiguous [B,T,H,W,Cout] tensor")
         a.add = add.data_ptr()
-    second_launch = None
     out_norm = None
     if keep_raw and post_norm is None:
         raise ValueError("ltxmi.conv3d: keep_raw is for post_norm")
@@ -445,13 +444,15 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
         for t in (scale, shift):
             if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, c_norm) or not t.is_cuda):
                 raise ValueError("ltxmi.conv3d: post_norm scale / shift must be contiguous fp32 [B, C] device tensors")
-        a.post_norm, a.post_scale, a.post_shift, a.post_eps = 1, _ptr(scale), _ptr(shift), eps
         if keep_raw:
             out_norm = torch.empty_like(out)
-            a.y_norm = out_norm.data_ptr()
-    # (after the norm request is in the arguments: at 512 input channels the split is only worth it when the norm rides along)
+        if CONV_SECOND_OUTPUT_FUSE if keep_raw else CONV_POST_NORM_FUSE:
+            a.post_norm, a.post_scale, a.post_shift, a.post_eps = 1, _ptr(scale), _ptr(shift), eps
+            if keep_raw:
+                a.y_norm = out_norm.data_ptr()
     # Scratch for the channel-split form of the wide, short layers (ltxmi_conv3d_args.workspace): one buffer per (device, stream),
-    # grown on demand, shared by every call on that stream (stream-ordered: the next call's writes follow this call's reads)
+    # grown on demand, shared by every call on that stream (stream-ordered: the next call's writes follow this call's reads).  Asked
+    # with the norm request in place (at 512 input channels the split pays only when the norm rides along), as the launch sees it.
     if CONV_SPLIT:
         want = int(lib.ltxmi_conv3d_workspace_bytes(ctypes.byref(a)))
         if want > 0:
@@ -462,10 +463,9 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
                     _conv_workspace.clear()
                 ws = _conv_workspace[key] = torch.empty(want, dtype=torch.uint8, device=x.device)
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    if post_norm is not None:
-        if not (CONV_SECOND_OUTPUT_FUSE if keep_raw else CONV_POST_NORM_FUSE) or not lib.ltxmi_conv3d_fuses_post_norm(ctypes.byref(a)):
-            a.post_norm, a.post_scale, a.post_shift, a.post_eps, a.y_norm = 0, None, None, 0.0, None
-            second_launch = (scale, shift, eps)
+    if a.post_norm and not lib.ltxmi_conv3d_fuses_post_norm(ctypes.byref(a)):
+        a.post_norm, a.post_scale, a.post_shift, a.post_eps, a.y_norm = 0, None, None, 0.0, None
+    second_launch = post_norm if post_norm is not None and not a.post_norm else None
     # (watched either by shape alone or by shape + epilogue: "plain" / "add" / "post_norm" / "second_output")
     kind = ("second_output" if a.y_norm else "post_norm") if a.post_norm else ("add" if add is not None else "plain")
     tok = _prof_begin(("conv3d", B * oT * oH * oW, Cin, Cout, int(d2s)), ("conv3d", B * oT * oH * oW, Cin, Cout, int(d2s), kind))

@@ -228,6 +228,97 @@ int main() {
     c.algo = 4;
     if (ltxmi_conv3d_workspace_bytes(&c) != 0) { fprintf(stderr, "FAIL workspace_bytes(eight-wave form asked for)\n"); ++g_bad; }
 
+    // The plan behind both queries, pinned over every convolution of the VAE decoder and encoder and of the latent upsampler
+    // at the sizes of the 768 x 512 x 97 generation (latent 13 x 16 x 24), with each epilogue the layer can run, under
+    // algo 0 .. 4: the workspace a call asks for, and whether it fuses post_norm without / with that workspace attached.
+    enum { ADD = 1, NORM = 2, YNORM = 4, D2S = 8, STRIDE2 = 16, PER_FRAME = 32 };
+    struct ConvCase { int T, H, W, Cin, Cout, causal, pad_replicate, time_pad_zeros, flags; int64_t ws[5]; const char* fuses; };
+    static const ConvCase conv_cases[] = {
+        // decoder
+        {13, 16, 24, 128, 1024, 0, 1, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 128, 1024, 0, 1, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 128, 1024, 0, 1, 0, 2, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 128, 1024, 0, 1, 0, 7, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 1024, 1024, 0, 1, 0, 0, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 1024, 0, 1, 0, 1, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0000000000"},
+        {13, 16, 24, 1024, 1024, 0, 1, 0, 2, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 1024, 0, 1, 0, 7, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 4096, 0, 1, 0, 8, {245366784ll, 0, 245366784ll, 245366784ll, 0}, "0000000000"},
+        {13, 16, 24, 1024, 4096, 0, 1, 0, 14, {245366784ll, 0, 245366784ll, 245366784ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 4096, 0, 1, 0, 10, {245366784ll, 0, 245366784ll, 245366784ll, 0}, "0000000000"},
+        {25, 32, 48, 512, 512, 0, 1, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 512, 0, 1, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 512, 0, 1, 0, 2, {157286400ll, 0, 157286400ll, 157286400ll, 0}, "0100010100"},
+        {25, 32, 48, 512, 512, 0, 1, 0, 7, {157286400ll, 0, 157286400ll, 157286400ll, 0}, "0100010100"},
+        {25, 32, 48, 512, 2048, 0, 1, 0, 8, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 2048, 0, 1, 0, 14, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 2048, 0, 1, 0, 10, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 0, 1, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 0, 1, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 0, 1, 0, 2, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 0, 1, 0, 7, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 1024, 0, 1, 0, 8, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 1024, 0, 1, 0, 14, {0, 0, 0, 0, 0}, "1100111100"},
+        {49, 64, 96, 256, 1024, 0, 1, 0, 10, {0, 0, 0, 0, 0}, "0000000000"},
+        {97, 128, 192, 128, 128, 0, 1, 0, 0, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 128, 0, 1, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {97, 128, 192, 128, 128, 0, 1, 0, 2, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 128, 0, 1, 0, 7, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 48, 0, 1, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        // encoder
+        {97, 128, 192, 64, 128, 1, 0, 0, 0, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 128, 1, 0, 0, 0, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 128, 1, 0, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {97, 128, 192, 128, 128, 1, 0, 0, 2, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 128, 1, 0, 0, 7, {0, 0, 0, 0, 0}, "1100111100"},
+        {97, 128, 192, 128, 256, 1, 0, 0, 16, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 1, 0, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 1, 0, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 1, 0, 0, 2, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 256, 1, 0, 0, 7, {0, 0, 0, 0, 0}, "0000000000"},
+        {49, 64, 96, 256, 512, 1, 0, 0, 16, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 512, 1, 0, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 512, 1, 0, 0, 1, {0, 0, 0, 0, 0}, "0000000000"},
+        {25, 32, 48, 512, 512, 1, 0, 0, 2, {157286400ll, 0, 157286400ll, 157286400ll, 0}, "0100010100"},
+        {25, 32, 48, 512, 512, 1, 0, 0, 7, {157286400ll, 0, 157286400ll, 157286400ll, 0}, "0100010100"},
+        {25, 32, 48, 512, 1024, 1, 0, 0, 16, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 1024, 1024, 1, 0, 0, 0, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 1024, 1, 0, 0, 1, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0000000000"},
+        {13, 16, 24, 1024, 1024, 1, 0, 0, 2, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 1024, 1, 0, 0, 7, {61341696ll, 0, 61341696ll, 61341696ll, 0}, "0100010100"},
+        {13, 16, 24, 1024, 136, 1, 0, 0, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        // latent upsampler
+        {13, 16, 24, 128, 512, 0, 0, 1, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 512, 512, 0, 0, 1, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 16, 24, 512, 2048, 0, 0, 1, 32, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 32, 48, 512, 512, 0, 0, 1, 0, {0, 0, 0, 0, 0}, "0000000000"},
+        {13, 32, 48, 512, 128, 0, 0, 1, 0, {0, 0, 0, 0, 0}, "0000001100"},
+    };
+    for (const ConvCase& k : conv_cases) {
+        for (int algo = 0; algo < 5; ++algo) {
+            memset(&c, 0, sizeof c);
+            c.x = p; c.w = p; c.bias = p; c.y = p;
+            c.B = 1; c.T = k.T; c.H = k.H; c.W = k.W; c.Cin = k.Cin; c.Cout = k.Cout;
+            c.causal = k.causal; c.pad_replicate = k.pad_replicate; c.time_pad_zeros = k.time_pad_zeros; c.algo = algo;
+            if (k.flags & ADD) c.add = p;
+            if (k.flags & NORM) { c.post_norm = 1; c.post_scale = pf; c.post_shift = pf; c.post_eps = 1e-8f; }
+            if (k.flags & YNORM) c.y_norm = pf + 64;
+            if (k.flags & D2S) { c.d2s = 1; c.residual = p; c.res_channels = k.Cin; }
+            if (k.flags & STRIDE2) c.stride_t = c.stride_hw = 2;
+            if (k.flags & PER_FRAME) c.kernel_t = 1;
+            const int64_t ws = ltxmi_conv3d_workspace_bytes(&c);
+            const int bare = ltxmi_conv3d_fuses_post_norm(&c);
+            c.workspace = pf; c.workspace_bytes = ws;
+            const int with_ws = ltxmi_conv3d_fuses_post_norm(&c);
+            if (ws != k.ws[algo] || bare != k.fuses[2 * algo] - '0' || with_ws != k.fuses[2 * algo + 1] - '0') {
+                fprintf(stderr, "FAIL conv plan %d x %d x %d, %d -> %d, flags %d, algo %d: workspace %lld (want %lld), fuses %d / %d "
+                                "(want %c / %c)\n", k.T, k.H, k.W, k.Cin, k.Cout, k.flags, algo, (long long)ws, (long long)k.ws[algo],
+                        bare, with_ws, k.fuses[2 * algo], k.fuses[2 * algo + 1]);
+                ++g_bad;
+            }
+        }
+    }
+
     // ---- VAE pointwise / layout kernels, guidance, conditioning, upsampler
     expect_fail(ltxmi_pixelnorm_ada_silu_bf16(nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, 0.f, nullptr), "pixelnorm(NULL)");
     expect_fail(ltxmi_pixelnorm_ada_silu_bf16(p, p, 13 * 32 * 48, 512, 13 * 32 * 48, pf, pf, 1, 1e-6f, nullptr), "pixelnorm(no device)");
