@@ -142,6 +142,9 @@ int ltxmi_rmsnorm_rope_rstd_bf16(void* x, int64_t ldx, int32_t rows, int32_t D, 
  * Layout NHD like the seam: element (b, l, h, d) at  base + b*stride_b + l*stride_l + h*head_dim + d
  * (strides in elements; lets q,k,v alias slices of one fused [B,L,3*H*dh] projection buffer).
  * key_bias: optional fp32 [B, Lk] added to the scaled scores (broadcast over heads and queries).
+ *   Any finite value and -inf are accepted (NaN is not).  A value at or below -1e30 -- -inf, the most negative float32 /
+ *   bfloat16 that masked_fill-style callers write -- means "this key is removed": its weight is exactly 0.  A batch row
+ *   with EVERY key removed is undefined, as in torch's SDPA (finite masks such as -10000 on every key give the plain softmax).
  * head_dim in {64, 128}; Lq, Lk >= 1 (ragged tails are masked inside the kernel).
  * Kernels behind the entry point (chosen by shape, ltxmi_attention_kernel_id): the software-pipelined LDS-DMA kernels for
  * large bias-free shapes (head_dim 64: two waves per SIMD; head_dim 128: one wave per SIMD with the whole register file),

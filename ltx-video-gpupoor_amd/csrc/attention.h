@@ -62,6 +62,10 @@ enum AttnKernel : int {
     ATTN_DH128 = 4, ATTN_DH128_BIAS = 5, ATTN_PIPE128 = 6, ATTN_CROSS = 7,
 };
 constexpr int ATTN_CROSS_MAX_KEYS = 256;
+// key_bias contract (include/ltxmi.h): any finite value and -inf are accepted.  The bias-taking kernels clamp the bias, in the
+// units they stage it in (x log2(e), or / softmax_scale), to this floor: a key at or below it is removed (P = 0 exactly), and
+// -inf or an overflowing "most negative" mask never meets +inf or a zero operand as NaN.
+constexpr float ATTN_BIAS_FLOOR = -1e30f;
 
 // Launchers of the kernels in the other attention files: each runs the shape it is given (attn_select has chosen it)
 int launch_attn_pipe(AttnParams p, hipStream_t stream);

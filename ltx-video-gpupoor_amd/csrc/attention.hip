@@ -176,7 +176,10 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
         }
         if (HAS_BIAS && tid < KV_TILE) {
             const int key = k0 + tid;
-            breg = key < p.Lk ? biasb[key] * LOG2E : 0.f;
+            // clamped to a finite value: with -inf (or a finite mask that overflows here) on every key seen so far the
+            // running maximum would be -inf and x - m = -inf + inf = NaN.  Finite, such keys get a finite P that the
+            // rescale factor exp2(m_old - m_new) = 0 wipes out when the first kept key arrives; behind one, their P is 0.
+            breg = key < p.Lk ? fmaxf(biasb[key] * LOG2E, ATTN_BIAS_FLOOR) : 0.f;
         }
     };
     auto write_tile = [&](int buf) {

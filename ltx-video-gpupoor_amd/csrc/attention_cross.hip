@@ -89,9 +89,11 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
         if (tid < MAX_TILES * KV_TILE) {
             // The key bias rides on the QK^T product as one more k-step: K gets the columns [b', b' - bf16(b')] (hi + lo: exact to
             // 2^-16 relative), Q the columns [1, 1], with b' = bias / softmax_scale so that c (K Q^T + b') = c K Q^T + bias log2(e).
-            // Keys past Lk get -1e30 (finite: -inf would meet the zero columns of Q as NaN), i.e. P = 0.
-            float bv = -1e30f;
-            if (tid < p.Lk) bv = p.bias ? p.bias[(int64_t)b * p.bias_sb + tid] * (LOG2E / p.scale_log2e) : 0.f;
+            // Keys past Lk get -1e30 (finite: -inf would meet the zero columns of Q as NaN), i.e. P = 0.  A caller's bias is
+            // clamped to the same value: -inf, and finite "most negative" masks that overflow in the division by the scale,
+            // would otherwise come out as hi = -inf, lo = -inf - -inf = NaN.  At or below the clamp a key is removed.
+            float bv = ATTN_BIAS_FLOOR;
+            if (tid < p.Lk) bv = p.bias ? fmaxf(p.bias[(int64_t)b * p.bias_sb + tid] * (LOG2E / p.scale_log2e), ATTN_BIAS_FLOOR) : 0.f;
             const __bf16 hi = (__bf16)bv;
             const __bf16 lo = (__bf16)(bv - (float)hi);
             u32x4 w = {0u, 0u, 0u, 0u};

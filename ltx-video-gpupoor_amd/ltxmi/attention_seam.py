@@ -18,7 +18,10 @@ from . import ops
 def _key_bias_from_mask(attention_mask, B, Lk):
     """The seam receives the mask as [B, Lq|1, H|1, Lk] (it is transposed(1,2) before SDPA,
     :110-111).  The kernel supports a per-key bias shared by all heads and queries, which is
-    what the LTX cross-attention produces (transformer3d.py:411-415 -> attention.py:1026-1033)."""
+    what the LTX cross-attention produces (transformer3d.py:411-415 -> attention.py:1026-1033).
+    The values pass through unchanged (converted to fp32): 0 / -10000 as the DiT writes them, any finite soft bias, and the
+    -inf or ``torch.finfo(dtype).min`` of masked_fill-style callers, which the kernels read as "key removed" (at or below
+    -1e30: weight exactly 0).  A batch row with every key removed is undefined, as in torch's SDPA."""
     m = attention_mask
     if m.dim() != 4 or m.shape[0] != B or m.shape[-1] != Lk:
         raise ValueError(f"pay_attention: attention_mask must be [B, 1|Lq, 1|H, Lk], got {tuple(m.shape)}")

@@ -222,7 +222,9 @@ def attention_kernel_id(B, H, Lq, Lk, dh, has_key_bias=False, k_stride_l=None, v
 def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None, rope=None, out_segments=None,
               redo_counter=None, force_exact=False):
     """q [B,Lq,H,dh], k/v [B,Lk,H,dh] (NHD; batch and token strides free, (H,dh) contiguous).
-    key_bias: fp32 [B,Lk] additive (broadcast over heads and queries).
+    key_bias: fp32 [B,Lk] additive (broadcast over heads and queries).  Any finite value and -inf are accepted; a value at
+    or below -1e30 (-inf, ``torch.finfo(...).min``) means "key removed": its weight is exactly 0.  A batch row with every key
+    removed is undefined, as in torch's SDPA.
     q_norm = (rowsumsq fp32 [B*Lq, H*dh/64] from ``gemm(..., rowsumsq=)`` OR the finalised factor fp32 [B*Lq] from
     ``rmsnorm_rope_(..., rstd_of=)``, weight bf16 [H*dh], eps): q is the raw projection output and is RMS-normalised over
     all heads (+ rotated with rope = (cos [period, H*dh], sin, period)) while the kernel loads it.
