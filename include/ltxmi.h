@@ -102,7 +102,11 @@ int ltxmi_gemm_bf16(const ltxmi_gemm_args* args, void* stream);
  *   scale[r,c] = scale_table[c] + scale_temb[g*temb_ld + c],  g = r / rows_per_group (same for shift)
  * Replaces norm1/norm2 + `*= 1+scale; += shift`  attention.py:233-251, 314-320 and
  * norm_out + modulation transformer3d.py:489-502 (kind = LTXMI_NORM_LAYER).
- * D % 8 == 0, D <= 8192.
+ * D % 8 == 0, D <= 8192 (else LTXMI_ERR_UNSUPPORTED and nothing is written).  LayerNorm's variance is computed about
+ * the mean (mean first, then the sum of (x - mean)^2 over the row held in registers), not as E[x^2] - mean^2: a row whose
+ * mean is hundreds of standard deviations keeps its variance.  y may be x (in place, same ldx): every 16-byte chunk is
+ * read and written by the same lane, and read before it is written.  One wave per row, fixed order: the result does not
+ * depend on scheduling.
  * ------------------------------------------------------------------------------- */
 typedef enum ltxmi_norm_kind { LTXMI_NORM_RMS = 0, LTXMI_NORM_LAYER = 1 } ltxmi_norm_kind;
 
@@ -317,7 +321,10 @@ int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* args);
 /* PixelNorm (pixel_norm.py:5-12, eps 1e-8) -> optional (1+scale)*x+shift per (batch, channel)
  * (ResnetBlock3D AdaLN, causal_video_autoencoder.py:1206-1243, Decoder tail :771-795)
  * -> optional SiLU; NDHWC rows of C channels; scale/shift fp32 [B, C] or NULL.
- * rows_per_batch = T*H*W.  C % 8 == 0, C <= 4096. */
+ * rows_per_batch = T*H*W.  C % 8 == 0, C <= 8192.  y may be x (in place: each 16-byte chunk is read and written by the
+ * same lane).  C = 64 / 128 / 256 with 16-byte aligned scale / shift takes a kernel that holds several rows per wave;
+ * other widths and unaligned tables take the row-per-wave kernel, which sums the squares in another order (results
+ * agree to fp32 rounding, not bit for bit). */
 int ltxmi_pixelnorm_ada_silu_bf16(const void* x, void* y, int64_t rows, int32_t C,
                                   int64_t rows_per_batch, const float* scale, const float* shift,
                                   int32_t apply_silu, float eps, void* stream);
@@ -326,7 +333,8 @@ int ltxmi_pixelnorm_ada_silu_bf16(const void* x, void* y, int64_t rows, int32_t 
 int ltxmi_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
 /* Channel LayerNorm with affine over NDHWC rows (norm3 of res_x_y blocks,
- * causal_video_autoencoder.py:1068-1077,1170-1174). */
+ * causal_video_autoencoder.py:1068-1077,1170-1174).  C % 8 == 0, C <= 8192.  Variance about the mean, as
+ * ltxmi_norm_modulate_bf16; y may be x (in place). */
 int ltxmi_layernorm_affine_bf16(const void* x, void* y, int64_t rows, int32_t C,
                                 const void* gamma, const void* beta, float eps, void* stream);
 
@@ -401,7 +409,12 @@ int ltxmi_image_cond_noise(void* latents, const void* init_latents, const void* 
  * ltxmi_conv3d_ndhwc_bf16 with kernel_t / time_pad_zeros.
  *   groupnorm_silu: x [samples, S, C] channels-last -> y = silu(GroupNorm(groups)(x) * gamma + beta
  *                   (+ residual)); ResBlock.forward :30-39 and initial_norm/activation :121-123.
- *                   samples = b (dims 3) or b*f (dims 2).  workspace: >= samples*(2C + 2*groups) floats.
+ *                   samples = b (dims 3) or b*f (dims 2).  workspace: >= samples * (nblk * 2C + 2 * groups) floats,
+ *                   nblk = max(1, 2048 / samples) (integer division); it need not be zeroed.  The statistics are
+ *                   shifted sums (each channel about its value in the sample's first row), so the variance is taken
+ *                   about the mean and survives |mean| >> std; they are per-block partials added in block order, no
+ *                   atomics: the result does not depend on scheduling (run-to-run bit-reproducible).  The activation
+ *                   is read twice and written once.  y may be x (in place).
  *   pixel_shuffle2d: x [frames, H, W, 4C] with channel (p1*2 + p2)*C + c -> y [frames, 2H, 2W, C]
  *                   (PixelShuffleND(2) :93-96 with the conv rows packed (p1 p2 c)).
  *   adain_filter:   per (b, c) plane: out = lerp(x, (x - mean_x)/std_x * std_ref + mean_ref, factor);

@@ -51,20 +51,29 @@ __global__ __launch_bounds__(256) void norm_modulate_kernel(
             c[j] = load_chunk(xr + ch * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                s1 += c[j].v[e];
-                s2 += c[j].v[e] * c[j].v[e];
+                if (LAYER) s1 += c[j].v[e];
+                else s2 += c[j].v[e] * c[j].v[e];
             }
         }
     }
-    s2 = wave_sum(s2);
-    float mean = 0.f, rstd;
+    float mean = 0.f;
     if (LAYER) {
-        s1 = wave_sum(s1);
-        mean = s1 / D;
-        rstd = rsqrtf(fmaxf(s2 / D - mean * mean, 0.f) + eps);
-    } else {
-        rstd = rsqrtf(s2 / D + eps);
+        // variance about the mean, from the values already in registers (E[x^2] - mean^2 in fp32 loses the variance
+        // once |mean| is a few hundred standard deviations): one more butterfly, no more memory traffic
+        mean = wave_sum(s1) / D;
+        s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            if (lane + 64 * j < nchunk) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float d = c[j].v[e] - mean;
+                    s2 += d * d;
+                }
+            }
+        }
     }
+    const float rstd = rsqrtf(wave_sum(s2) / D + eps);
     const int64_t g = (int64_t)(row / rows_per_group) * temb_ld;
     uint16_t* yr = y + (int64_t)row * ldy;
 #pragma unroll
@@ -239,23 +248,29 @@ __global__ __launch_bounds__(256) void layernorm_affine_kernel(const uint16_t* _
     const int nchunk = C >> 3;
     const uint16_t* xr = x + row * C;
     Chunk c[NCH];
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f;
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
         const int ch = lane + 64 * j;
         if (ch < nchunk) {
             c[j] = load_chunk(xr + ch * 8);
 #pragma unroll
+            for (int e = 0; e < 8; ++e) s1 += c[j].v[e];
+        }
+    }
+    const float mean = wave_sum(s1) / C;
+    float s2 = 0.f;                                        // variance about the mean, as norm_modulate_kernel<LAYER>
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        if (lane + 64 * j < nchunk) {
+#pragma unroll
             for (int e = 0; e < 8; ++e) {
-                s1 += c[j].v[e];
-                s2 += c[j].v[e] * c[j].v[e];
+                const float d = c[j].v[e] - mean;
+                s2 += d * d;
             }
         }
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const float mean = s1 / C;
-    const float rstd = rsqrtf(fmaxf(s2 / C - mean * mean, 0.f) + eps);
+    const float rstd = rsqrtf(wave_sum(s2) / C + eps);
     uint16_t* yr = y + row * C;
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {

@@ -12,10 +12,13 @@ namespace ltxmi {
 constexpr int UP_THREADS = 256;
 
 // ---------------------------------------------------------------- GroupNorm, channels-last
-// x [Bn, S, C]: per (sample, channel) sum / sum of squares -> ws[Bn][C][2] (fp32, zeroed by the caller).
-// Thread -> (row offset, 8-channel slot); a block reduces its rows through LDS and issues ONE atomic
-// pair per channel.  C/8 is a power of two <= 256.
-__global__ void gn_stats_kernel(const uint16_t* __restrict__ x, float* __restrict__ ws, int64_t S, int C,
+// x [Bn, S, C]: per (sample, row block, channel) SHIFTED sum / sum of squares -> part[Bn][blocks][C][2] (fp32), the shift
+// being the channel's value in the sample's first row: with d = x - pivot the sums stay of the order of the data's spread,
+// so the variance does not drown in mean^2 (E[x^2] - mean^2 in fp32 lost it once |mean| was a few hundred standard
+// deviations), and the activation is still read only once for the statistics.  Thread -> (row offset, 8-channel slot); a
+// block reduces its rows through LDS and writes ONE pair per channel into its own slot: no atomics, so the result does not
+// depend on the order in which blocks finish.  C/8 is a power of two <= 256.
+__global__ void gn_stats_kernel(const uint16_t* __restrict__ x, float* __restrict__ part, int64_t S, int C,
                                 int rows_per_block) {
     __shared__ float red[UP_THREADS][17];                 // [thread][8 sums + 8 squares], padded
     const int slots = C >> 3;
@@ -25,14 +28,19 @@ __global__ void gn_stats_kernel(const uint16_t* __restrict__ x, float* __restric
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
     int64_t r1 = r0 + rows_per_block;
     if (r1 > S) r1 = S;
-    float s[8], q[8];
+    float s[8], q[8], pv[8];
+    {
+        const u32x4 w = *(const u32x4*)(x + b * S * C + slot * 8);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { pv[2 * k] = bf_lo(w[k]); pv[2 * k + 1] = bf_hi(w[k]); }
+    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) s[k] = q[k] = 0.f;
     for (int64_t r = r0 + roff; r < r1; r += rpi) {
         const u32x4 w = *(const u32x4*)(x + (b * S + r) * C + slot * 8);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float lo = bf_lo(w[k]), hi = bf_hi(w[k]);
+            const float lo = bf_lo(w[k]) - pv[2 * k], hi = bf_hi(w[k]) - pv[2 * k + 1];
             s[2 * k] += lo; q[2 * k] += lo * lo;
             s[2 * k + 1] += hi; q[2 * k + 1] += hi * hi;
         }
@@ -40,29 +48,64 @@ __global__ void gn_stats_kernel(const uint16_t* __restrict__ x, float* __restric
 #pragma unroll
     for (int k = 0; k < 8; ++k) { red[threadIdx.x][k] = s[k]; red[threadIdx.x][8 + k] = q[k]; }
     __syncthreads();
-    // thread t < slots*16 finalises value (slot, k): sum over the rpi row-offset copies
+    // thread t < slots*16 finalises value (slot, k): sum over the rpi row-offset copies, in order
+    float* dst = part + (b * gridDim.x + blockIdx.x) * (int64_t)C * 2;
     for (int v = threadIdx.x; v < slots * 16; v += UP_THREADS) {
         const int sl = v >> 4, k = v & 15;
         float acc = 0.f;
         for (int j = 0; j < rpi; ++j) acc += red[j * slots + sl][k];
         const int ch = sl * 8 + (k & 7);
-        atomicAdd(ws + ((b * C + ch) << 1) + (k >> 3), acc);
+        dst[(ch << 1) + (k >> 3)] = acc;
     }
 }
 
-// ws[Bn][C][2] -> stat[Bn][G][2] = (mean, rstd) over S * C/G values
-__global__ void gn_finalize_kernel(const float* __restrict__ ws, float* __restrict__ stat, int C, int G, int64_t S,
-                                   float eps, int total) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int b = i / G, g = i % G, cg = C / G;
-    float s = 0.f, q = 0.f;
-    for (int c = g * cg; c < (g + 1) * cg; ++c) { s += ws[((int64_t)b * C + c) * 2]; q += ws[((int64_t)b * C + c) * 2 + 1]; }
-    const float n = (float)S * (float)cg;
-    const float mean = s / n;
-    const float var = fmaxf(q / n - mean * mean, 0.f);      // biased, like nn.GroupNorm
-    stat[i * 2] = mean;
-    stat[i * 2 + 1] = rsqrtf(var + eps);
+// part[Bn][blocks][C][2] -> stat[Bn][G][2] = (mean, rstd) over S * C/G values; one workgroup per (sample, group).
+// The block partials of a channel are added in block order (a fixed subset per thread, then the threads in order), each
+// channel becomes (mean_c, M2_c) about its own mean, and the channels of the group are combined by the parallel-variance
+// formula M2 = sum M2_c + S sum (mean_c - mean)^2.  In double: a few thousand values per group, nothing on the clock.
+constexpr int GN_MAX_CG = 2048;
+__global__ __launch_bounds__(UP_THREADS) void gn_finalize_kernel(const uint16_t* __restrict__ x,
+                                                                 const float* __restrict__ part, float* __restrict__ stat,
+                                                                 int C, int G, int64_t S, int blocks, float eps) {
+    __shared__ double ts[UP_THREADS], tq[UP_THREADS];
+    __shared__ double ch_mean[GN_MAX_CG], ch_m2[GN_MAX_CG];
+    const int t = threadIdx.x;
+    const int b = blockIdx.x / G, g = blockIdx.x % G, cg = C / G;      // cg is a power of two
+    const int lanes = cg < UP_THREADS ? cg : UP_THREADS;               // channels in flight
+    const int tpc = UP_THREADS / lanes;                                // threads per channel
+    const int cl = t % lanes, sub = t / lanes;
+    for (int c0 = 0; c0 < cg; c0 += lanes) {
+        const int c = g * cg + c0 + cl;
+        double s = 0.0, q = 0.0;
+        for (int blk = sub; blk < blocks; blk += tpc) {
+            const float* p = part + (((int64_t)b * blocks + blk) * C + c) * 2;
+            s += (double)p[0];
+            q += (double)p[1];
+        }
+        ts[t] = s;
+        tq[t] = q;
+        __syncthreads();
+        if (sub == 0) {
+            for (int j = 1; j < tpc; ++j) { s += ts[j * lanes + cl]; q += tq[j * lanes + cl]; }
+            const double pivot = (double)bf2f(x[(int64_t)b * S * C + c]);
+            ch_mean[c0 + cl] = pivot + s / (double)S;
+            ch_m2[c0 + cl] = q - s * s / (double)S;
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        double ms = 0.0;
+        for (int c = 0; c < cg; ++c) ms += ch_mean[c];
+        const double mean = ms / cg;
+        double m2 = 0.0;
+        for (int c = 0; c < cg; ++c) {
+            const double d = ch_mean[c] - mean;
+            m2 += ch_m2[c] + (double)S * d * d;
+        }
+        const double var = fmax(m2 / ((double)S * cg), 0.0);           // biased, like nn.GroupNorm
+        stat[blockIdx.x * 2] = (float)mean;
+        stat[blockIdx.x * 2 + 1] = rsqrtf((float)var + eps);
+    }
 }
 
 // y = silu((x - mean) * rstd * gamma + beta (+ residual))
@@ -194,24 +237,19 @@ extern "C" int ltxmi_groupnorm_silu_bf16(const void* x, void* y, const void* res
                   LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_groupnorm_silu_bf16: C=%d must be 8 * 2^k <= 2048 and divisible by groups=%d", C, groups);
     hipStream_t s = (hipStream_t)stream;
-    float* sums = workspace;                                   // [samples][C][2]
-    float* stat = workspace + (int64_t)samples * C * 2;        // [samples][groups][2]
-    if (hipMemsetAsync(sums, 0, sizeof(float) * (size_t)samples * C * 2, s) != hipSuccess) {
-        set_error("ltxmi_groupnorm_silu_bf16: hipMemsetAsync failed");
-        return LTXMI_ERR_LAUNCH;
-    }
     // ~2048 blocks over the (rows, samples) grid
     int64_t want = 2048 / samples;
     if (want < 1) want = 1;
     int64_t rpb = (S + want - 1) / want;
     const int rpi = UP_THREADS / slots;
     rpb = (rpb + rpi - 1) / rpi * rpi;
-    const unsigned gx = (unsigned)((S + rpb - 1) / rpb);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(gx, samples), dim3(UP_THREADS), 0, s, (const uint16_t*)x, sums, S, C,
+    const unsigned gx = (unsigned)((S + rpb - 1) / rpb);       // <= want = max(1, 2048 / samples)
+    float* part = workspace;                                   // [samples][gx][C][2], every entry written by gn_stats
+    float* stat = workspace + (int64_t)samples * want * C * 2; // [samples][groups][2]
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(gx, samples), dim3(UP_THREADS), 0, s, (const uint16_t*)x, part, S, C,
                        (int)rpb);
-    const int total = samples * groups;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((total + 255) / 256), dim3(256), 0, s, sums, stat, C, groups, S, eps,
-                       total);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(samples * groups), dim3(UP_THREADS), 0, s, (const uint16_t*)x, part, stat,
+                       C, groups, S, (int)gx, eps);
     const int64_t chunks = (int64_t)samples * S * slots;
     int64_t g = (chunks + UP_THREADS - 1) / UP_THREADS;
     if (g > 2048) g = 2048;

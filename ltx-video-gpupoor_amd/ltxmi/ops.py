@@ -628,7 +628,8 @@ def groupnorm_silu(x, gamma, beta, groups, eps, residual=None, samples=None, out
     samples = x.shape[0] if samples is None else samples
     S = x.numel() // C // samples
     out = torch.empty_like(x) if out is None else out
-    ws = torch.empty(samples * (2 * C + 2 * groups), dtype=torch.float32, device=x.device)
+    # per-block partial sums [samples][max(1, 2048 // samples)][C][2] + the statistics [samples][groups][2] (include/ltxmi.h)
+    ws = torch.empty(samples * (max(1, 2048 // samples) * 2 * C + 2 * groups), dtype=torch.float32, device=x.device)
     check(lib.ltxmi_groupnorm_silu_bf16(_ptr(x), _ptr(out), _ptr(residual), samples, S, C, groups, _ptr(gamma),
                                         _ptr(beta), eps, _ptr(ws), _stream()), "ltxmi_groupnorm_silu_bf16")
     return out

@@ -61,7 +61,7 @@ def norm_modulate(x, out, eps, kind, scale_table, scale_temb, shift_table, shift
     rows, D = x2.shape
     if kind == ops.NORM_LAYER:
         mean = x2.mean(-1, keepdim=True)
-        n = (x2 - mean) * torch.rsqrt((x2.pow(2).mean(-1, keepdim=True) - mean * mean).clamp_min(0) + eps)
+        n = (x2 - mean) * torch.rsqrt((x2 - mean).pow(2).mean(-1, keepdim=True) + eps)
     else:
         n = x2 * torch.rsqrt(x2.pow(2).mean(-1, keepdim=True) + eps)
     sc = scale_table.float()[None] + scale_temb.float().repeat_interleave(rows_per_group, dim=0)[:rows]
