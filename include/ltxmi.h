@@ -20,7 +20,8 @@
  *   - argument structs (ltxmi_*_args) MUST be zero-initialised before the fields in use are
  *     set (`ltxmi_gemm_args a = {0};` / memset): versions append optional fields at the tail
  *     (0.2: rowsumsq*, a_kblock* of ltxmi_gemm_args; q_rowsumsq*, q_norm*, rope_*, o_segment*
- *     of ltxmi_attn_args; 0.3: q_rstd*; 0.4: conv3d post_*; 0.5: redo_counter, force_exact of ltxmi_attn_args, y_norm, workspace of ltxmi_conv3d_args), and a zero there means "off".  A caller must be
+ *     of ltxmi_attn_args; 0.3: q_rstd*; 0.4: conv3d post_*; 0.5: redo_counter, force_exact of ltxmi_attn_args, y_norm, workspace of ltxmi_conv3d_args;
+ *     0.6: lse* of ltxmi_attn_args), and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
  *     switches its companion size / stride fields off whatever they hold.
  */
@@ -190,6 +191,16 @@ typedef struct ltxmi_attn_args {
      * it); force_exact != 0: every item takes the exact form at once (what a launch costs when nothing fits the range).
      * Ignored by the register-staged kernel, which has the exact form only. */
     uint32_t* redo_counter; int32_t force_exact;
+    /* 0.6 -- optional second output, the softmax_lse of flash-attn / xformers / torch's flash SDPA (the reference's flash and
+     * varlen back-ends, wan/modules/attention.py:344-372, and its ring, xdit_context_parallel.py:179-184, are built on it):
+     *   lse[b * lse_stride_b + h * lse_stride_h + l] = ln sum_j exp(softmax_scale * q_l . k_j + key_bias[b, j]),
+     * fp32, natural-log units, logical shape [B, H, Lq] with token stride 1 (lse_stride_h >= Lq, lse_stride_b >= H *
+     * lse_stride_h, 4-byte aligned; else LTXMI_ERR_INVALID_ARG).  It is computed from the very row sum (and running maximum)
+     * the kernel divides O by, so that sum_i exp(lse_i) O_i / sum_i exp(lse_i) over launches with disjoint key sets is the
+     * softmax over their union (ltxmi_attention_merge_bf16).  A removed key (bias at or below -1e30) contributes 0; a row with
+     * EVERY key removed reports -inf (its O stays undefined).  Every kernel behind the entry point writes it; the choice of
+     * kernel (ltxmi_attention_kernel_id) and O itself do not depend on it.  NULL = off: nothing is written. */
+    float* lse; int64_t lse_stride_b, lse_stride_h;
 } ltxmi_attn_args;
 
 int ltxmi_attention_fwd_bf16(const ltxmi_attn_args* args, void* stream);
@@ -202,6 +213,28 @@ int ltxmi_attention_fuses_qnorm(int32_t B, int32_t H, int32_t Lq, int32_t Lk, in
  * (batch, head)'s keys with 32-bit byte offsets and hand shapes whose rows span 2 GiB or more to the other kernels. */
 int ltxmi_attention_kernel_id(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t head_dim, int32_t has_key_bias,
                               int64_t k_stride_l, int64_t v_stride_l);
+
+/* Merge of n partial attention results over DISJOINT key sets for the same queries, in one launch (2 <= n <= 8): what the
+ * ring of the reference's sequence parallelism (xdit_context_parallel.py:179-184 -> xFuserLongContextAttention) does to its
+ * (out, lse) pair after every ring step, here once over all steps so that the result is rounded to bf16 once.  fp32 arithmetic:
+ *   m = max_i lse_i,  w_i = exp(lse_i - m),  o = sum_i w_i o_i / sum_i w_i,  lse = m + ln sum_i w_i.
+ * o_part[i]: bf16 [B, Lq, H, head_dim] as ltxmi_attn_args.o (batch / token strides in elements, multiples of 8, (H, head_dim)
+ * contiguous, 16-byte aligned); lse_part[i]: fp32 [B, H, Lq] as ltxmi_attn_args.lse.  o: the merged output, same layout (it
+ * may be one of the partials: every 16-byte chunk is read and written by the same lane); lse: optional merged lse, NULL = off.
+ * A partial with lse_i = -inf (every key of its set removed) is skipped by selection, its o_i -- undefined, NaN included --
+ * is not read; all n at -inf give lse = -inf and an undefined o.  head_dim % 8 == 0.  The segmented output geometry of
+ * ltxmi_attn_args (o_segment_len) is not offered here.  n outside 2 .. 8, a NULL partial or a misaligned / inconsistent lse:
+ * LTXMI_ERR_INVALID_ARG, before any launch. */
+#define LTXMI_ATTN_MERGE_MAX 8
+typedef struct ltxmi_attn_merge_args {
+    int32_t n;
+    const void*  o_part[LTXMI_ATTN_MERGE_MAX];   int64_t o_part_stride_b[LTXMI_ATTN_MERGE_MAX], o_part_stride_l[LTXMI_ATTN_MERGE_MAX];
+    const float* lse_part[LTXMI_ATTN_MERGE_MAX]; int64_t lse_part_stride_b[LTXMI_ATTN_MERGE_MAX], lse_part_stride_h[LTXMI_ATTN_MERGE_MAX];
+    void*  o;   int64_t o_stride_b, o_stride_l;
+    float* lse; int64_t lse_stride_b, lse_stride_h;
+    int32_t B, H, Lq, head_dim;
+} ltxmi_attn_merge_args;
+int ltxmi_attention_merge_bf16(const ltxmi_attn_merge_args* args, void* stream);
 
 /* The same row factor as a launch of its own (cross-attention's q, which has no k pass of equal row count to ride on):
  * rstd_out[r] = rsqrt(sum_j rowsumsq[r * rowsumsq_ld + j] / norm_dim + norm_eps), j < rowsumsq_blocks, r < rows. */

@@ -26,6 +26,8 @@ struct AttnParams {
     // diagnostics of the pipelined kernels' steady (reference-0) form: a device counter that every workgroup whose item had to
     // be redone in the exact form bumps once (nullptr = off), and a switch that sends EVERY item straight to the exact form
     uint32_t* redo_count; int force_exact;
+    // optional second output: lse[b * lse_sb + head * lse_sh + row] = ln sum_j exp(scale q.k_j + bias_j), fp32 (nullptr = off)
+    float* lse; int64_t lse_sb, lse_sh;
 
     __host__ __device__ __forceinline__ bool q_on_load() const { return q_ss != nullptr || q_rstd != nullptr; }
     // q's RMSNorm factor of row `row` of batch b (HD = H * head_dim, the normalised width)
@@ -44,6 +46,15 @@ struct AttnParams {
             for (int j = 0; j < q_ss_n; ++j) s2 += ss[j];
         }
         return rsqrtf(s2 / (float)HD + q_eps);
+    }
+
+    // The row's log-sum-exp from the kernel's OWN normaliser: l = the row sum O is divided by, taken against the reference
+    // m_log2 (the running / tile maximum in bits; 0 in the pipelined kernels' steady form).  removed: the maximum, in the
+    // units the bias was clamped in, sits at the clamp -- every key of the row was removed and the row reports -inf.  Called inside
+    // a wave-uniform `if (p.lse)` in the epilogue by the lanes that hold a row's l and m.
+    __device__ __forceinline__ void store_lse(int b, int head, int row, float m_log2, float l, bool removed) const {
+        constexpr float LN2 = 0.6931471805599453f;
+        lse[(int64_t)b * lse_sb + (int64_t)head * lse_sh + row] = removed ? -INFINITY : (m_log2 + __log2f(l)) * LN2;
     }
 
     __device__ __forceinline__ int64_t o_row(int row) const {
@@ -66,6 +77,8 @@ constexpr int ATTN_CROSS_MAX_KEYS = 256;
 // units they stage it in (x log2(e), or / softmax_scale), to this floor: a key at or below it is removed (P = 0 exactly), and
 // -inf or an overflowing "most negative" mask never meets +inf or a zero operand as NaN.
 constexpr float ATTN_BIAS_FLOOR = -1e30f;
+// A row whose maximum score sits at the floor (to the 2^-16 of the short-key kernel's hi + lo bias split) has every key removed
+constexpr float ATTN_ROW_REMOVED = 0.99f * ATTN_BIAS_FLOOR;
 
 // Launchers of the kernels in the other attention files: each runs the shape it is given (attn_select has chosen it)
 int launch_attn_pipe(AttnParams p, hipStream_t stream);

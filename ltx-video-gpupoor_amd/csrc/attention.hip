@@ -411,6 +411,11 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
         const float l0 = __shfl(lT[i][0], r & 15, 64), l1 = __shfl(lT[i][1], r & 15, 64);
         const float l = (r & 16) ? l1 : l0;
         const float inv = 1.0f / l;
+        if (p.lse != nullptr) {
+            // (wave-uniform; m_run is this lane's query's maximum: raw scores without a bias, bits with one or with FOLD)
+            const float m2 = (HAS_BIAS || FOLD) ? m_run[i] : m_run[i] * c;
+            if (hh == 0 && q_row[i] < p.Lq) p.store_lse(b, head, q_row[i], m2, l, HAS_BIAS && m_run[i] <= ATTN_ROW_REMOVED);
+        }
         // A lane holds 8-byte pieces of ONE output row; stored from registers, every store instruction
         // would touch 32 different 128-byte lines with 16 bytes each (store-issue bound, cdna guide T21).
         // The 32 x DH block goes through a per-wave LDS scratch (the K/V stages are free now) and leaves
@@ -515,6 +520,12 @@ extern "C" int ltxmi_attention_fwd_bf16(const ltxmi_attn_args* a, void* stream) 
     p.redo_count = a->redo_counter; p.force_exact = a->force_exact != 0;
     LTXMI_REQUIRE(a->o_segment_len >= 0 && a->o_stride_segment % 8 == 0, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_attention_fwd_bf16: bad output segment geometry");
+    p.lse = a->lse; p.lse_sb = a->lse_stride_b; p.lse_sh = a->lse_stride_h;
+    if (a->lse)
+        LTXMI_REQUIRE((((uintptr_t)a->lse) & 3) == 0 && a->lse_stride_h >= a->Lq &&
+                          (a->B == 1 ? a->lse_stride_b >= 0 : a->lse_stride_b >= (int64_t)a->H * a->lse_stride_h),
+                      LTXMI_ERR_INVALID_ARG,
+                      "ltxmi_attention_fwd_bf16: lse must be 4-byte aligned with lse_stride_h >= Lq and lse_stride_b >= H * lse_stride_h");
     if (a->q_rowsumsq || a->q_rstd) {
         LTXMI_REQUIRE(a->q_norm_weight && (((uintptr_t)a->q_norm_weight) & 15) == 0 &&
                           (a->q_rstd ? (((uintptr_t)a->q_rstd) & 3) == 0

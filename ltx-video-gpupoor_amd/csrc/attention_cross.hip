@@ -304,7 +304,12 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
         // ---- O = O^T / l: query r's sum sits in lane (r & 15), register (r >> 4).  The 32 x 64 block leaves in two halves of
         // 32 columns through the wave's 2-KB scratch: 16 bytes per lane, 16 whole 64-byte row halves per store instruction.
         const float l0 = __shfl(lT[0], r & 15, 64), l1v = __shfl(lT[1], r & 15, 64);
-        const float inv = 1.0f / ((r & 16) ? l1v : l0);
+        const float lrow = (r & 16) ? l1v : l0;
+        const float inv = 1.0f / lrow;
+        if (p.lse != nullptr) {
+            // (wave-uniform) the row's reference in bits is c * mt = -nmc; mt = -nmc / c sits at the bias clamp when every key is removed
+            if (hh == 0 && q0 + r < row_end) p.store_lse(b, head, q0 + r, -nmc, lrow, -nmc / c <= ATTN_ROW_REMOVED);
+        }
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
 #pragma unroll

@@ -507,7 +507,13 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
     // ---- epilogue: O = O^T / l, through a per-wave LDS scratch so that rows leave whole (attention.hip)
     auto store = [&](Blk& X, int blk) {
         const float l0 = __shfl(X.l[0], L.r & 15, 64), l1 = __shfl(X.l[1], L.r & 15, 64);
-        const float inv = 1.0f / ((L.r & 16) ? l1 : l0);
+        const float lrow = (L.r & 16) ? l1 : l0;
+        const float inv = 1.0f / lrow;
+        if (p.lse != nullptr) {
+            // (wave-uniform) the steady form's reference is 0; the exact form's is the running maximum X.m (bits if QSCALED)
+            const int row = qt * Q_PER_WG + wave * 64 + 32 * blk + L.r;
+            if (L.hh == 0 && row < p.Lq) p.store_lse(b, head, row, REDO ? (QSCALED ? X.m : X.m * c) : 0.f, lrow, false);
+        }
         char* scr = smem + (wave * 2 + blk) * (32 * ROW_BYTES);
 #pragma unroll
         for (int d = 0; d < 2; ++d)

@@ -466,7 +466,13 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
     auto store = [&](Blk& X, int blk) {
         settle_o(X.o);
         const float l0 = __shfl(X.l[0], L.r & 15, 64), l1 = __shfl(X.l[1], L.r & 15, 64);
-        const float inv = 1.0f / ((L.r & 16) ? l1 : l0);
+        const float lrow = (L.r & 16) ? l1 : l0;
+        const float inv = 1.0f / lrow;
+        if (p.lse != nullptr) {
+            // (wave-uniform) both forms take P against the row's reference X.m (raw scores): running maximum or fixed
+            const int row = qt * Q_PER_WG + wave * 64 + 32 * blk + L.r;
+            if (L.hh == 0 && row < p.Lq) p.store_lse(b, head, row, X.m * c, lrow, false);
+        }
         char* scr = smem + (wave * 2 + blk) * (32 * ROW_BYTES);
 #pragma unroll
         for (int d = 0; d < ND; ++d)

@@ -41,7 +41,22 @@ class AttnArgs(ctypes.Structure):
                 ("rope_cos", c_void_p), ("rope_sin", c_void_p), ("rope_stride_b", c_int64), ("rope_stride_l", c_int64),
                 ("o_segment_len", c_int), ("o_stride_segment", c_int64),
                 ("q_rstd", c_void_p), ("q_rstd_stride_b", c_int64), ("q_rstd_stride_l", c_int64),
-                ("redo_counter", c_void_p), ("force_exact", c_int)]
+                ("redo_counter", c_void_p), ("force_exact", c_int),
+                ("lse", c_void_p), ("lse_stride_b", c_int64), ("lse_stride_h", c_int64)]
+
+
+ATTN_MERGE_MAX = 8
+
+
+class AttnMergeArgs(ctypes.Structure):
+    _fields_ = [("n", c_int),
+                ("o_part", c_void_p * ATTN_MERGE_MAX), ("o_part_stride_b", c_int64 * ATTN_MERGE_MAX),
+                ("o_part_stride_l", c_int64 * ATTN_MERGE_MAX),
+                ("lse_part", c_void_p * ATTN_MERGE_MAX), ("lse_part_stride_b", c_int64 * ATTN_MERGE_MAX),
+                ("lse_part_stride_h", c_int64 * ATTN_MERGE_MAX),
+                ("o", c_void_p), ("o_stride_b", c_int64), ("o_stride_l", c_int64),
+                ("lse", c_void_p), ("lse_stride_b", c_int64), ("lse_stride_h", c_int64),
+                ("B", c_int), ("H", c_int), ("Lq", c_int), ("head_dim", c_int)]
 
 
 class Conv3dArgs(ctypes.Structure):
@@ -71,6 +86,7 @@ SIGNATURES = {
     "ltxmi_qkv_norm_rope_pack_bf16": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                               c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "ltxmi_attention_fwd_bf16": (c_int, [ctypes.POINTER(AttnArgs), c_void_p]),
+    "ltxmi_attention_merge_bf16": (c_int, [ctypes.POINTER(AttnMergeArgs), c_void_p]),
     "ltxmi_attention_fuses_qnorm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "ltxmi_attention_kernel_id": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64]),
     "ltxmi_silu_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -213,6 +213,11 @@ class AttnProcessor2_0:
     epilogue that updates ``residual`` in place and returns it; without it the plain
     ``to_out[0]`` result is returned exactly like the reference."""
 
+    def attend(self, qkv_list, is_cross, **kw):
+        """The attention call itself: ``pay_attention``, the reference's seam.  A processor that computes self-attention
+        some other way over the same q / k / v production (``distributed.RingAttnProcessor``) replaces this one step."""
+        return pay_attention(qkv_list, **kw)
+
     def __call__(self, attn: Attention, hidden_states_wrapper, freqs_cis, encoder_hidden_states=None,
                  attention_mask=None, temb=None, skip_layer_mask=None, skip_layer_strategy=None,
                  fused_residual=None, *args, **kwargs):
@@ -334,8 +339,8 @@ class AttnProcessor2_0:
                 if attention_mask.dim() != 3 or attention_mask.shape[1] != 1:
                     raise NotImplementedError("ltxmi.AttnProcessor2_0: attention_mask must be a [B,1,Lk] bias")
                 mask4 = attention_mask.reshape(B, 1, 1, Lk)
-            a4 = pay_attention([q4, k4, v4], attention_mask=mask4, softmax_scale=attn.scale,
-                               q_norm=q_fused[0] if q_fused else None, rope=q_fused[1] if q_fused else None)   # [B,N,H,dh]
+            a4 = self.attend([q4, k4, v4], is_cross, attention_mask=mask4, softmax_scale=attn.scale,
+                             q_norm=q_fused[0] if q_fused else None, rope=q_fused[1] if q_fused else None)   # [B,N,H,dh]
             a3 = a4.view(B, N, D)
             if host_mask is not None and any(m != 1.0 for m in host_mask):
                 m_dev = skip_layer_mask.reshape(B).to(torch.float32)

@@ -1,4 +1,4 @@
-"""Sequence parallelism (Ulysses) for ``Transformer3DModel`` over RCCL/xGMI.
+"""Sequence parallelism (Ulysses, ring, and their hybrid) for ``Transformer3DModel`` over RCCL/xGMI.
 
 The reference carries an unbound USP implementation for its Wan model built on the third-party
 ``xfuser`` package (wan/distributed/xdit_context_parallel.py:66-192: ``usp_dit_forward`` chunks the
@@ -16,7 +16,15 @@ provides the same two entry points for the LTX DiT, written directly on ``torch.
     at once (each peer pair its own link) and is not ring/per-link bound;
   * the model output [B, N/P, C] is all-gathered once per forward.
 
-Requires H % P == 0 and N % P == 0 (and, for per-frame timesteps, whole frames per rank).
+The Ulysses mode requires H % P == 0 and N % P == 0 (and, for per-frame timesteps, whole frames per rank).
+
+The reference's xFuserLongContextAttention is USP: Ulysses AND ring.  The ring half (``ring_attn_forward``,
+``RingAttnProcessor``, ``enable_sequence_parallel(mode="ring")``) keeps every head on every rank and splits the KEYS
+instead: each rank attends its own queries to one K/V shard at a time while the next shard travels round the ring by
+point-to-point send / receive, and the P partial results -- each with the log-sum-exp the kernel divided it by
+(``ops.attention(return_lse=True)``) -- are merged in one launch (``ops.attention_merge``).  No divisibility of the head
+count is asked for (Wan's 12 heads on 8 ranks).  ``usp_attn_forward(ring_degree=R)`` is the hybrid: Ulysses inside groups
+of world / R consecutive ranks, the ring across the groups.
 """
 import math
 from typing import Callable, Optional
@@ -24,7 +32,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from .attention import BasicTransformerBlock, SkipLayerStrategy
+from .attention import AttnProcessor2_0, BasicTransformerBlock, SkipLayerStrategy
 
 
 # ------------------------------------------------------------------ layout + collectives
@@ -79,18 +87,103 @@ def head_to_seq_shard(o, group=None):
     return recv.permute(1, 2, 0, 3, 4).reshape(B, Nl, world * Hl, dh)            # chunk i = heads of rank i
 
 
-def usp_attn_forward(qkv, softmax_scale, group=None, attn_fn: Optional[Callable] = None):
+def usp_attn_forward(qkv, softmax_scale, group=None, attn_fn: Optional[Callable] = None, ring_degree=1,
+                     merge_fn: Optional[Callable] = None):
     """Ulysses self-attention on a packed, already normed/roped projection buffer (generic form, any attention
     function; the product path below is the zero-copy form of the same exchange).
     qkv: [B, N/P, 3, H, dh] -> returns [B, N/P, H, dh].
     Name from wan/distributed/xdit_context_parallel.py:149; the signature there (``self, x, seq_lens, grid_sizes, freqs,
-    dtype``) belongs to ``WanSelfAttention.forward`` and is not reproduced."""
+    dtype``) belongs to ``WanSelfAttention.forward`` and is not reproduced.
+
+    ``ring_degree`` R > 1: the hybrid of the reference's USP, world = U x R.  The all-to-alls run inside groups of U
+    consecutive ranks (rank r then holds H / U heads over its group's U N/P tokens), the ring of ``ring_attention`` runs
+    across the groups (ranks r, r + U, ... share a head subset and own one token block each); ``attn_fn`` must then return
+    ``(o, lse)`` and ``merge_fn`` merge such pairs (defaults: the kernels).  H % U == 0 is all that is asked of the heads.
+    Every rank of ``group`` must make the call (the first one creates the sub-groups)."""
+    if ring_degree > 1:
+        ulysses_group, ring_group = hybrid_groups(ring_degree, group)
+        full = seq_to_head_shard(qkv, ulysses_group)
+        o = ring_attention(full[:, :, 0], full[:, :, 1], full[:, :, 2], softmax_scale, ring_group, attn_fn, merge_fn)
+        return head_to_seq_shard(o.contiguous(), ulysses_group)
     if attn_fn is None:
         from . import ops
         attn_fn = lambda q, k, v, scale: ops.attention(q, k, v, softmax_scale=scale)   # noqa: E731
     full = seq_to_head_shard(qkv, group)
     o = attn_fn(full[:, :, 0], full[:, :, 1], full[:, :, 2], softmax_scale)
     return head_to_seq_shard(o.contiguous(), group)
+
+
+# ------------------------------------------------------------------ ring
+RING_MAX = 8          # partial results one ``ops.attention_merge`` launch takes
+
+_HYBRID_GROUPS = {}
+
+
+def hybrid_groups(ring_degree, group=None):
+    """(ulysses_group, ring_group) of the calling rank for world = U x ring_degree: the Ulysses groups are runs of U
+    consecutive ranks, the ring groups the ranks U apart.  ``dist.new_group`` is a collective over the default group: the
+    first call must be made by every rank (all sub-groups are created by all ranks, in one order); later calls are cached."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if ring_degree < 1 or world % ring_degree != 0:
+        raise ValueError(f"ring degree {ring_degree} does not divide the sequence-parallel degree {world}")
+    key = (group, ring_degree)
+    hit = _HYBRID_GROUPS.get(key)
+    if hit is None:
+        U = world // ring_degree
+        ranks = dist.get_process_group_ranks(group) if group is not None else list(range(world))
+        ulysses = [dist.new_group([ranks[g * U + u] for u in range(U)]) for g in range(ring_degree)]
+        rings = [dist.new_group([ranks[g * U + u] for g in range(ring_degree)]) for u in range(U)]
+        hit = _HYBRID_GROUPS[key] = (ulysses[rank // U], rings[rank % U])
+    return hit
+
+
+def ring_attention(q, k, v, softmax_scale, group=None, attn_fn: Optional[Callable] = None,
+                   merge_fn: Optional[Callable] = None):
+    """Attention of the local queries q [B, Nq, H, dh] over the keys of EVERY rank of ``group``, each rank contributing its
+    shard k / v [B, Nk, H, dh] (equal shapes on all ranks).  The K/V shards travel round the ring -- rank r sends to r + 1
+    and receives from r - 1, ``dist.batch_isend_irecv``, nothing else -- and the transfer of shard s + 1 is posted BEFORE
+    the attention over shard s is issued, so it runs underneath it.  ``attn_fn(q, k, v, scale) -> (o, lse)`` gives one
+    partial result per shard, ``merge_fn(outs, lses) -> o`` finishes them at once: the result is rounded once, not once
+    per ring step (the reference's ring updates its out / lse pair after every step, xdit_context_parallel.py:179-184)."""
+    if attn_fn is None or merge_fn is None:
+        from . import ops
+        if attn_fn is None:
+            attn_fn = lambda q_, k_, v_, scale: ops.attention(q_, k_, v_, softmax_scale=scale, return_lse=True)   # noqa: E731
+        if merge_fn is None:
+            merge_fn = ops.attention_merge
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if world == 1:
+        return attn_fn(q, k, v, softmax_scale)[0]
+    if world > RING_MAX:
+        raise ValueError(f"ring degree {world} exceeds the {RING_MAX} partial results one merge takes; "
+                         "use usp_attn_forward(ring_degree=) with a smaller ring")
+    nxt, prv = (rank + 1) % world, (rank - 1) % world
+    if group is not None:
+        nxt, prv = dist.get_global_rank(group, nxt), dist.get_global_rank(group, prv)
+    cur = torch.stack((k, v), dim=2)                    # [B, Nk, 2, H, dh]: what travels, one buffer per step
+    outs, lses = [], []
+    for s in range(world):
+        reqs = ()
+        if s + 1 < world:
+            nbuf = torch.empty_like(cur)
+            reqs = dist.batch_isend_irecv([dist.P2POp(dist.isend, cur, nxt, group),
+                                           dist.P2POp(dist.irecv, nbuf, prv, group)])
+        o, lse = attn_fn(q, cur[:, :, 0], cur[:, :, 1], softmax_scale)
+        outs.append(o)
+        lses.append(lse)
+        if s + 1 < world:
+            for r in reqs:
+                r.wait()
+            cur = nbuf
+    return merge_fn(outs, lses)
+
+
+def ring_attn_forward(qkv, softmax_scale, group=None, attn_fn: Optional[Callable] = None,
+                      merge_fn: Optional[Callable] = None):
+    """Ring self-attention on a packed, already normed / roped projection buffer, beside ``usp_attn_forward``:
+    qkv [B, N/P, 3, H, dh] (this rank's tokens, ALL heads) -> [B, N/P, H, dh].  No head ever changes rank, so H need not
+    divide P.  ``attn_fn`` returns ``(o, lse)``, ``merge_fn`` merges the P pairs (defaults: the kernels)."""
+    return ring_attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], softmax_scale, group, attn_fn, merge_fn)
 
 
 # ------------------------------------------------------------------ processor + model forward
@@ -193,8 +286,35 @@ class UlyssesAttnProcessor:
         return ops.gemm(a_blk0, w_o, b_o, **kb).view(B, Nl, -1)
 
 
-def enable_sequence_parallel(model, group=None, overlap=True, bind_forward=False, exchange_at_world_1=None):
-    """Install the Ulysses processor on every block's self-attention.
+class RingAttnProcessor(AttnProcessor2_0):
+    """Ring mode: AttnProcessor2_0 on the rank's token shard with ONE step replaced.  q / k / v are produced exactly as on
+    one rank -- the fused QKV projection, k's RMSNorm + RoPE pass with the shard's rows of ``freqs_cis`` (which also
+    finalises q's row factor), q's norm + RoPE applied by the attention kernel on load; every head is on every rank, so
+    the across-heads RMSNorm needs no exchange -- and the attention call becomes ``ring_attention`` over the group.  STG
+    blends, ``to_out`` and its fused gate / residual epilogue follow unchanged.  Cross-attention (text keys replicated on
+    every rank, queries sharded) stays the local call."""
+
+    def __init__(self, group=None):
+        self.group = group
+
+    def attend(self, qkv_list, is_cross, **kw):
+        if is_cross:
+            return super().attend(qkv_list, is_cross, **kw)
+        from . import ops
+        q, k, v = qkv_list
+        qkv_list.clear()
+        if kw.get("attention_mask") is not None:
+            raise NotImplementedError("RingAttnProcessor: a self-attention mask is not on this path")
+        extra = dict(q_norm=kw.get("q_norm"), rope=kw.get("rope"))
+        return ring_attention(q, k, v, kw.get("softmax_scale"), self.group,
+                              lambda q_, k_, v_, scale: ops.attention(q_, k_, v_, softmax_scale=scale, return_lse=True, **extra))
+
+
+def enable_sequence_parallel(model, group=None, overlap=True, bind_forward=False, exchange_at_world_1=None, mode="ulysses"):
+    """Install the sequence-parallel processor on every block's self-attention: ``mode="ulysses"`` (the default) the
+    Ulysses processor, ``mode="ring"`` the ring processor (all heads on every rank, keys split; heads need not divide the
+    world size; the micro-batch overlap below is a Ulysses-mode feature and stays off).  ``usp_dit_forward``,
+    ``begin_generation`` and the interrupt agreement are the same in both modes.
 
     ``bind_forward`` (the reference's pattern for its Wan model, ``wan/text2video.py``: ``model.forward =
     types.MethodType(usp_dit_forward, model)``): rebind ``model.forward`` to ``usp_dit_forward`` so that an unchanged caller
@@ -207,11 +327,13 @@ def enable_sequence_parallel(model, group=None, overlap=True, bind_forward=False
     one micro-batch waits for its all-to-all (RCCL runs it on the process group's communication stream), the other
     one's projection / attention / to_out / FF kernels run.  Rows are computed independently of each other by every
     kernel, so the result is the same as without the split (tests: world size 2, torch.equal)."""
+    if mode not in ("ulysses", "ring"):
+        raise ValueError(f"enable_sequence_parallel: mode {mode!r} is not 'ulysses' or 'ring'")
     for blk in model.transformer_blocks:
         assert isinstance(blk, BasicTransformerBlock)
-        blk.attn1.set_processor(UlyssesAttnProcessor(group, exchange_at_world_1))
+        blk.attn1.set_processor(RingAttnProcessor(group) if mode == "ring" else UlyssesAttnProcessor(group, exchange_at_world_1))
     model._sp_group = group
-    model._sp_overlap = bool(overlap)
+    model._sp_overlap = bool(overlap) and mode == "ulysses"
     model._sp_interrupt = _InterruptAgreement()
     model.__dict__.pop("forward", None)
     if bind_forward:

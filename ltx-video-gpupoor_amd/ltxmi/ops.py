@@ -220,7 +220,7 @@ def attention_kernel_id(B, H, Lq, Lk, dh, has_key_bias=False, k_stride_l=None, v
 
 
 def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None, rope=None, out_segments=None,
-              redo_counter=None, force_exact=False):
+              redo_counter=None, force_exact=False, return_lse=False, lse=None):
     """q [B,Lq,H,dh], k/v [B,Lk,H,dh] (NHD; batch and token strides free, (H,dh) contiguous).
     key_bias: fp32 [B,Lk] additive (broadcast over heads and queries).  Any finite value and -inf are accepted; a value at
     or below -1e30 (-inf, ``torch.finfo(...).min``) means "key removed": its weight is exactly 0.  A batch row with every key
@@ -231,7 +231,11 @@ def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None,
     out_segments = (tokens per segment, elements between segments): ``out`` is segment 0's [B, segment, H, dh] view of a
     buffer whose token axis is cut into such segments (the Ulysses return all-to-all's send buffer).
     redo_counter (diagnostic): int32 device tensor of one element, incremented once per (batch, head, query tile) item the
-    pipelined kernels had to run again in the exact online-softmax form; force_exact: every item in that form."""
+    pipelined kernels had to run again in the exact online-softmax form; force_exact: every item in that form.
+    return_lse: return ``(out, lse)`` with lse fp32 [B, H, Lq] = ln sum_j exp(scale q.k_j + key_bias_j), the normaliser
+    ``out`` was divided by (-inf for a row with every key removed) -- allocated here or written into ``lse=`` (which
+    implies return_lse); ``attention_merge`` combines such pairs over disjoint key sets.  ``out`` and the kernel chosen do
+    not depend on it."""
     _chk_bf16(q, k, v, out)
     B, Lq, H, dh = q.shape
     Lk = k.shape[1]
@@ -294,10 +298,54 @@ def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None,
             raise ValueError("ltxmi.attention: redo_counter must be a CUDA int32 tensor of one element")
         a.redo_counter = redo_counter.data_ptr()
     a.force_exact = int(bool(force_exact))
+    if return_lse or lse is not None:
+        if lse is None:
+            lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+        _chk_lse(lse, B, H, Lq, "ltxmi.attention: lse")
+        a.lse, a.lse_stride_b, a.lse_stride_h = lse.data_ptr(), lse.stride(0), lse.stride(1)
     tok = _prof_begin(("attention", B, H, Lq, Lk, dh))
     check(lib.ltxmi_attention_fwd_bf16(ctypes.byref(a), _stream()), "ltxmi_attention_fwd_bf16")
     _prof_end(tok)
-    return out
+    return (out, lse) if lse is not None else out
+
+
+def _chk_lse(lse, B, H, Lq, what):
+    if lse.dtype != torch.float32 or not lse.is_cuda or tuple(lse.shape) != (B, H, Lq) or lse.stride(2) != 1:
+        raise ValueError(f"{what} must be a CUDA fp32 [B, H, Lq] = {(B, H, Lq)} tensor with contiguous tokens")
+
+
+def attention_merge(outs, lses, out=None, return_lse=False, lse=None):
+    """Merge 2 .. 8 partial attention results over disjoint key sets for the same queries in one launch
+    (``ltxmi_attention_merge_bf16``): outs[i] bf16 [B, Lq, H, dh] and lses[i] fp32 [B, H, Lq] as ``attention(...,
+    return_lse=True)`` returns them.  fp32: w_i = exp(lse_i - max lse), out = sum w_i outs[i] / sum w_i, rounded to bf16
+    once; a partial with lse_i = -inf is skipped (its out may hold anything).  Returns out, or (out, merged lse) with
+    return_lse / ``lse=``.  ``out`` may be one of the partials."""
+    n = len(outs)
+    if n != len(lses) or not 2 <= n <= _lib.ATTN_MERGE_MAX:
+        raise ValueError(f"ltxmi.attention_merge: {n} outputs / {len(lses)} lse tensors, need 2 .. {_lib.ATTN_MERGE_MAX} of each")
+    _chk_bf16(*outs, out)
+    B, Lq, H, dh = outs[0].shape
+    if out is None:
+        out = torch.empty((B, Lq, H, dh), dtype=BF16, device=outs[0].device)
+    a = _lib.AttnMergeArgs()
+    a.n = n
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        if tuple(o.shape) != (B, Lq, H, dh) or o.stride(3) != 1 or o.stride(2) != dh:
+            raise ValueError("ltxmi.attention_merge: partial outputs must be [B, Lq, H, dh] with (heads, head_dim) contiguous")
+        _chk_lse(l, B, H, Lq, f"ltxmi.attention_merge: lses[{i}]")
+        a.o_part[i], a.o_part_stride_b[i], a.o_part_stride_l[i] = o.data_ptr(), o.stride(0), o.stride(1)
+        a.lse_part[i], a.lse_part_stride_b[i], a.lse_part_stride_h[i] = l.data_ptr(), l.stride(0), l.stride(1)
+    if tuple(out.shape) != (B, Lq, H, dh) or out.stride(3) != 1 or out.stride(2) != dh:
+        raise ValueError("ltxmi.attention_merge: out must be [B, Lq, H, dh] with (heads, head_dim) contiguous")
+    a.o, a.o_stride_b, a.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    if return_lse or lse is not None:
+        if lse is None:
+            lse = torch.empty((B, H, Lq), dtype=torch.float32, device=out.device)
+        _chk_lse(lse, B, H, Lq, "ltxmi.attention_merge: lse")
+        a.lse, a.lse_stride_b, a.lse_stride_h = lse.data_ptr(), lse.stride(0), lse.stride(1)
+    a.B, a.H, a.Lq, a.head_dim = B, H, Lq, dh
+    check(lib.ltxmi_attention_merge_bf16(ctypes.byref(a), _stream()), "ltxmi_attention_merge_bf16")
+    return (out, lse) if lse is not None else out
 
 
 def qkv_norm_rope_pack(qkv, B, Nl, D, P, q_weight, k_weight, eps, cos=None, sin=None, rope_period=0, out=None):
