@@ -11,7 +11,7 @@ Per step (pipeline_ltx_video.py:1104-1256):
                                                                    ltxmi_guidance_step_bf16
 
 The reference's per-step host work (``skip_layer_mask.min()`` per block, ``.item()`` calls,
-Python float timesteps) is replaced by host-side schedule scalars computed once; no
+Python float timesteps) is replaced by host-side schedule scalars computed once (``_StepPlan``); no
 host<->device synchronisation happens inside the loop.
 """
 import copy
@@ -36,28 +36,43 @@ class ConditioningItem:
     media_y: Optional[int] = None
 
 
+def _refuse(rows):
+    """Walk ``(refused, exception type, message)`` rows in order and raise the first one that applies."""
+    for refused, error, message in rows:
+        if refused:
+            raise error("ltxmi.LTXVideoPipeline: " + message)
+
+
+def _shape(x):
+    return None if x is None else tuple(x.shape)
+
+
+def _resize_frames(video, height, width):
+    """(b, c, f, h, w) -> (b, c, f, height, width): torch's bilinear resize, frame by frame (host-side pre- / post-processing)."""
+    frames = video.transpose(1, 2).flatten(0, 1)
+    frames = torch.nn.functional.interpolate(frames, size=(height, width), mode="bilinear", align_corners=False)
+    return frames.unflatten(0, (-1, video.shape[2])).transpose(1, 2)
+
+
 def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, timesteps=None, max_timestep=1.0,
                        skip_initial_inference_steps=0, skip_final_inference_steps=0, **kwargs):
     """pipeline_ltx_video.py:125-198: the scheduler's (or the given) schedule, minus skipped head/tail
     steps, truncated to ``max_timestep``; the scheduler is re-set to exactly the returned list."""
-    if timesteps is not None:
-        scheduler.set_timesteps(timesteps=timesteps, device=device, **kwargs)
-    else:
-        scheduler.set_timesteps(num_inference_steps, device=device, **kwargs)
-    ts = list(scheduler.host_timesteps)
-    n = len(ts)
-    if (skip_initial_inference_steps < 0 or skip_final_inference_steps < 0
-            or skip_initial_inference_steps + skip_final_inference_steps >= n):
-        raise ValueError("invalid skip inference step values: must be non-negative and the sum of "
-                         "skip_initial_inference_steps and skip_final_inference_steps must be less than the "
-                         "number of inference steps")
-    ts = ts[skip_initial_inference_steps: n - skip_final_inference_steps]
+    asked = {"num_inference_steps": num_inference_steps} if timesteps is None else {"timesteps": timesteps}
+    scheduler.set_timesteps(device=device, **asked, **kwargs)
+    schedule = list(scheduler.host_timesteps)
+    head, tail = skip_initial_inference_steps, skip_final_inference_steps
+    if head < 0 or tail < 0 or head + tail >= len(schedule):
+        raise ValueError(f"ltxmi.retrieve_timesteps: skip_initial_inference_steps={head} and skip_final_inference_steps="
+                         f"{tail} must be >= 0 and leave at least one of the {len(schedule)} steps")
+    schedule = schedule[head: len(schedule) - tail]
     if max_timestep < 1.0:
-        if max_timestep < min(ts):
-            raise ValueError(f"max_timestep {max_timestep} is smaller than the minimum timestep {min(ts)}")
-        ts = [t for t in ts if t <= max_timestep]
-    scheduler.set_timesteps(timesteps=ts, device=device, **kwargs)
-    return list(scheduler.host_timesteps), len(ts)
+        if max_timestep < min(schedule):
+            raise ValueError(f"ltxmi.retrieve_timesteps: max_timestep={max_timestep} lies below the whole schedule "
+                             f"(its last step is {min(schedule)})")
+        schedule = [t for t in schedule if t <= max_timestep]
+    scheduler.set_timesteps(timesteps=schedule, device=device, **kwargs)
+    return list(scheduler.host_timesteps), len(schedule)
 
 
 class LTXVideoPipeline:
@@ -71,11 +86,8 @@ class LTXVideoPipeline:
                  prompt_enhancer_image_caption_model=None, prompt_enhancer_image_caption_processor=None,
                  prompt_enhancer_llm_model=None, prompt_enhancer_llm_tokenizer=None,
                  allowed_inference_steps: Optional[List[float]] = None):
-        self.tokenizer = tokenizer
-        self.text_encoder = text_encoder
-        self.vae = vae
-        self.transformer = transformer
-        self.scheduler = scheduler
+        self.tokenizer, self.text_encoder = tokenizer, text_encoder
+        self.vae, self.transformer, self.scheduler = vae, transformer, scheduler
         self.patchifier = patchifier or SymmetricPatchifier(patch_size=1)
         self.prompt_enhancer_image_caption_model = prompt_enhancer_image_caption_model
         self.prompt_enhancer_image_caption_processor = prompt_enhancer_image_caption_processor
@@ -92,98 +104,72 @@ class LTXVideoPipeline:
     # ---- prompt side (pipeline_ltx_video.py:315-485, 513-606): host checks and the hand-over to the caller's T5 ----
     def check_inputs(self, prompt, height, width, negative_prompt, prompt_embeds=None, negative_prompt_embeds=None,
                      prompt_attention_mask=None, negative_prompt_attention_mask=None, enhance_prompt=False):
-        if height % 8 != 0 or width % 8 != 0:
-            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
-        if prompt is not None and prompt_embeds is not None:
-            raise ValueError("Cannot forward both `prompt` and `prompt_embeds`. Please make sure to only forward one of the two.")
-        if prompt is None and prompt_embeds is None:
-            raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and `prompt_embeds` undefined.")
-        if prompt is not None and not isinstance(prompt, (str, list)):
-            raise ValueError(f"`prompt` has to be of type `str` or `list` but is {type(prompt)}")
-        if prompt is not None and negative_prompt_embeds is not None:
-            raise ValueError("Cannot forward both `prompt` and `negative_prompt_embeds`. Please make sure to only forward one of the two.")
-        if negative_prompt is not None and negative_prompt_embeds is not None:
-            raise ValueError("Cannot forward both `negative_prompt` and `negative_prompt_embeds`. Please make sure to only forward one of the two.")
-        if prompt_embeds is not None and prompt_attention_mask is None:
-            raise ValueError("Must provide `prompt_attention_mask` when specifying `prompt_embeds`.")
-        if negative_prompt_embeds is not None and negative_prompt_attention_mask is None:
-            raise ValueError("Must provide `negative_prompt_attention_mask` when specifying `negative_prompt_embeds`.")
-        if prompt_embeds is not None and negative_prompt_embeds is not None:
-            if prompt_embeds.shape != negative_prompt_embeds.shape:
-                raise ValueError("`prompt_embeds` and `negative_prompt_embeds` must have the same shape when passed directly, but"
-                                 f" got: `prompt_embeds` {prompt_embeds.shape} != `negative_prompt_embeds` {negative_prompt_embeds.shape}.")
-            if prompt_attention_mask.shape != negative_prompt_attention_mask.shape:
-                raise ValueError("`prompt_attention_mask` and `negative_prompt_attention_mask` must have the same shape when passed "
-                                 f"directly, but got: {prompt_attention_mask.shape} != {negative_prompt_attention_mask.shape}.")
-        if enhance_prompt:
-            raise NotImplementedError("ltxmi: enhance_prompt (Florence / LLM prompt rewriting) is outside this path")
+        """Refuse argument sets the call cannot honour; the first row that applies is the one reported."""
+        text, embeds, negative_embeds = prompt is not None, prompt_embeds is not None, negative_prompt_embeds is not None
+        pair = embeds and negative_embeds
+        _refuse([
+            (height % 8 or width % 8, ValueError, f"height and width must be multiples of 8, got {height} x {width}"),
+            (text and embeds, ValueError, "prompt and prompt_embeds are alternatives, pass one of them"),
+            (not text and not embeds, ValueError, "one of prompt / prompt_embeds is required"),
+            (text and not isinstance(prompt, (str, list)), ValueError,
+             f"prompt is a str or a list of str, not {type(prompt).__name__}"),
+            (text and negative_embeds, ValueError, "negative_prompt_embeds goes with prompt_embeds, not with a text prompt"),
+            (negative_prompt is not None and negative_embeds, ValueError,
+             "negative_prompt and negative_prompt_embeds are alternatives, pass one of them"),
+            (embeds and prompt_attention_mask is None, ValueError, "prompt_embeds comes with its prompt_attention_mask"),
+            (negative_embeds and negative_prompt_attention_mask is None, ValueError,
+             "negative_prompt_embeds comes with its negative_prompt_attention_mask"),
+            (pair and _shape(prompt_embeds) != _shape(negative_prompt_embeds), ValueError,
+             f"prompt_embeds {_shape(prompt_embeds)} and negative_prompt_embeds {_shape(negative_prompt_embeds)} differ in shape"),
+            (pair and _shape(prompt_attention_mask) != _shape(negative_prompt_attention_mask), ValueError,
+             f"prompt_attention_mask {_shape(prompt_attention_mask)} and negative_prompt_attention_mask "
+             f"{_shape(negative_prompt_attention_mask)} differ in shape"),
+            (enhance_prompt, NotImplementedError, "enhance_prompt (Florence / LLM prompt rewriting) is outside this path"),
+        ])
+
+    def _encode_texts(self, texts, num_tokens, device, dtype):
+        """``texts`` (stripped; padded / truncated to ``num_tokens``) through the caller's tokenizer and text encoder:
+        (embeds (n, num_tokens, d) in ``dtype``, attention mask (n, num_tokens)), both on ``device``."""
+        if self.text_encoder is None or self.tokenizer is None:
+            raise RuntimeError("ltxmi.LTXVideoPipeline.encode_prompt: text prompts (the negative one included) need the "
+                               "caller's T5 (`tokenizer=` and `text_encoder=` at construction) -- the text encoder is outside "
+                               "this library; alternatively pass the embeddings and their attention masks")
+        t5_device = next(self.text_encoder.parameters()).device
+        tokens = self.tokenizer([text.strip() for text in texts], padding="max_length", max_length=num_tokens,
+                                truncation=True, add_special_tokens=True, return_tensors="pt")
+        mask = tokens.attention_mask.to(t5_device)
+        embeds = self.text_encoder(tokens.input_ids.to(t5_device), attention_mask=mask)[0]
+        return embeds.to(device=device, dtype=dtype), mask.to(device)
 
     @staticmethod
-    def _text_preprocessing(text):                                                       # :592-600
-        if not isinstance(text, (tuple, list)):
-            text = [text]
-        return [t.strip() for t in text]
+    def _per_image(embeds, mask, num_images):
+        """Every row ``num_images`` times, prompt-major: (p0, p0, p1, p1, ...)."""
+        return embeds.repeat_interleave(num_images, dim=0), mask.repeat_interleave(num_images, dim=0)
 
     def encode_prompt(self, prompt, do_classifier_free_guidance: bool = True, negative_prompt: str = "",
                       num_images_per_prompt: int = 1, device=None, prompt_embeds=None, negative_prompt_embeds=None,
                       prompt_attention_mask=None, negative_prompt_attention_mask=None,
                       text_encoder_max_tokens: int = 256, **kwargs):
-        """:315-485.  Tokenise, run the caller's text encoder, repeat per image; the T5 itself is not part of
-        this library -- without ``text_encoder`` / ``tokenizer`` a string prompt is an explicit error."""
-        if device is None:
-            device = self._execution_device
-        if prompt is not None and isinstance(prompt, str):
-            batch_size = 1
-        elif prompt is not None and isinstance(prompt, list):
-            batch_size = len(prompt)
-        else:
-            batch_size = prompt_embeds.shape[0]
-        max_length = text_encoder_max_tokens
-        text_enc_device = None
-        if prompt_embeds is None:
-            if self.text_encoder is None or self.tokenizer is None:
-                raise RuntimeError("ltxmi.LTXVideoPipeline.encode_prompt: a string prompt needs the caller's T5 "
-                                   "(`tokenizer=` and `text_encoder=` at construction) -- the text encoder is outside "
-                                   "this library; alternatively pass prompt_embeds / prompt_attention_mask")
-            text_enc_device = next(self.text_encoder.parameters()).device
-            prompt = self._text_preprocessing(prompt)
-            text_inputs = self.tokenizer(prompt, padding="max_length", max_length=max_length, truncation=True,
-                                         add_special_tokens=True, return_tensors="pt")
-            prompt_attention_mask = text_inputs.attention_mask.to(text_enc_device).to(device)
-            prompt_embeds = self.text_encoder(text_inputs.input_ids.to(text_enc_device),
-                                              attention_mask=prompt_attention_mask)[0]
-        if self.text_encoder is not None:
-            dtype = self.text_encoder.dtype
-        elif self.transformer is not None:
-            dtype = self.transformer.dtype
-        else:
-            dtype = None
-        prompt_embeds = prompt_embeds.to(dtype=dtype, device=device)
-        bs_embed, seq_len, _ = prompt_embeds.shape
-        prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs_embed * num_images_per_prompt, seq_len, -1)
-        prompt_attention_mask = prompt_attention_mask.repeat(1, num_images_per_prompt).view(bs_embed * num_images_per_prompt, -1)
-        if do_classifier_free_guidance and negative_prompt_embeds is None:
-            if self.text_encoder is None or self.tokenizer is None:
-                raise RuntimeError("ltxmi.LTXVideoPipeline.encode_prompt: the negative prompt needs the caller's T5 too")
-            text_enc_device = next(self.text_encoder.parameters()).device
-            uncond_tokens = self._text_preprocessing(negative_prompt) * batch_size
-            uncond_input = self.tokenizer(uncond_tokens, padding="max_length", max_length=prompt_embeds.shape[1],
-                                          truncation=True, return_attention_mask=True, add_special_tokens=True,
-                                          return_tensors="pt")
-            negative_prompt_attention_mask = uncond_input.attention_mask.to(text_enc_device)
-            negative_prompt_embeds = self.text_encoder(uncond_input.input_ids.to(text_enc_device),
-                                                       attention_mask=negative_prompt_attention_mask)[0]
-        if do_classifier_free_guidance:
-            seq_len = negative_prompt_embeds.shape[1]
-            negative_prompt_embeds = negative_prompt_embeds.to(dtype=dtype, device=device)
-            negative_prompt_embeds = negative_prompt_embeds.repeat(1, num_images_per_prompt, 1).view(
-                batch_size * num_images_per_prompt, seq_len, -1)
-            negative_prompt_attention_mask = negative_prompt_attention_mask.repeat(1, num_images_per_prompt).view(
-                bs_embed * num_images_per_prompt, -1)
-        else:
-            negative_prompt_embeds = None
-            negative_prompt_attention_mask = None
-        return prompt_embeds, prompt_attention_mask, negative_prompt_embeds, negative_prompt_attention_mask
+        """:315-485.  The positive and (under guidance) the negative (embeds, mask) pair, each either encoded by the
+        caller's text encoder or taken as given, cast to the text encoder's (else the transformer's) dtype and repeated
+        per image.  The negative text is encoded once per prompt, at the positive pair's token length.  The T5 itself
+        is not part of this library: text without ``text_encoder`` / ``tokenizer`` is an explicit error."""
+        device = self._execution_device if device is None else device
+        owner = self.text_encoder if self.text_encoder is not None else self.transformer
+        dtype = None if owner is None else owner.dtype
+
+        def pair(texts, embeds, mask, num_tokens, copies=1):
+            if embeds is not None:
+                return embeds.to(device=device, dtype=dtype), mask
+            texts = [texts] if isinstance(texts, str) else list(texts)
+            return self._encode_texts(texts * copies, num_tokens, device, dtype)
+
+        positive = pair(prompt, prompt_embeds, prompt_attention_mask, text_encoder_max_tokens)
+        if not do_classifier_free_guidance:
+            return (*self._per_image(*positive, num_images_per_prompt), None, None)
+        num_prompts, num_tokens = positive[0].shape[:2]
+        negative = pair(negative_prompt, negative_prompt_embeds, negative_prompt_attention_mask, num_tokens, copies=num_prompts)
+        return (*self._per_image(*positive, num_images_per_prompt), *self._per_image(*negative, num_images_per_prompt))
 
     @staticmethod
     def postprocess(image, output_type):
@@ -201,99 +187,92 @@ class LTXVideoPipeline:
                         vae_per_channel_normalize: bool = True):
         """pipeline_ltx_video.py:632-710: (b, c, f, h, w) latents = pure noise, or the given latents / the encoded
         ``media_items`` noised to ``timestep``.  The noise is drawn in PATCHIFIED order (b, f*h*w, c) (:696-699)."""
-        if isinstance(generator, list) and len(generator) != latent_shape[0]:
-            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective "
-                             f"batch size of {latent_shape[0]}. Make sure the batch size matches the length of the generators.")
-        assert latents is None or media_items is None, \
-            "Cannot provide both latents and media_items. Please provide only one of the two."
+        batch, channels, frames, rows, cols = latent_shape
+        if isinstance(generator, list) and len(generator) != batch:
+            raise ValueError(f"ltxmi.LTXVideoPipeline: {len(generator)} generators for a batch of {batch}")
+        assert latents is None or media_items is None, "ltxmi.LTXVideoPipeline: latents and media_items are alternatives"
         assert (latents is None and media_items is None) or timestep < 1.0, \
-            "Input media_item or latents are provided, but they will be replaced with noise."
+            "ltxmi.LTXVideoPipeline: at timestep 1 the given latents / media_items would be all noise (pass strength < 1)"
+        start = latents
         if media_items is not None:
-            latents = vae_encode(media_items.to(dtype=self.vae.dtype, device=self.vae.device), self.vae,
-                                 vae_per_channel_normalize=vae_per_channel_normalize)
-        if latents is not None:
-            assert tuple(latents.shape) == tuple(latent_shape), \
-                f"Latents have to be of shape {tuple(latent_shape)} but are {tuple(latents.shape)}."
-            latents = latents.to(device=device, dtype=dtype)
-        b, c, f, h, w = latent_shape
-        noise = torch.randn((b, f * h * w, c), generator=generator, device=device, dtype=dtype)
-        noise = self.patchifier.unpatchify(noise, h, w, c)
-        noise = noise * self.scheduler.init_noise_sigma
-        if latents is None:
-            return noise
-        return timestep * noise + (1 - timestep) * latents
+            start = vae_encode(media_items.to(dtype=self.vae.dtype, device=self.vae.device), self.vae,
+                               vae_per_channel_normalize=vae_per_channel_normalize)
+        if start is not None:
+            assert tuple(start.shape) == tuple(latent_shape), \
+                f"ltxmi.LTXVideoPipeline: latents {tuple(start.shape)} where the call needs {tuple(latent_shape)}"
+            start = start.to(device=device, dtype=dtype)
+        noise = torch.randn((batch, frames * rows * cols, channels), generator=generator, device=device, dtype=dtype)
+        noise = self.patchifier.unpatchify(noise, rows, cols, channels) * self.scheduler.init_noise_sigma
+        return noise if start is None else timestep * noise + (1 - timestep) * start
 
     # ---- conditioning (pipeline_ltx_video.py:1344-1690) ---------------------------------------
     # Setup-time token assembly: slicing / lerp on small latent tensors, once per call (not per step);
     # the encoder it feeds from and everything inside the loop run on libltxmi kernels.
     @staticmethod
     def resize_tensor(media_items, height, width):                                       # :748-760
-        """Host pre-processing (a torch bilinear resize per frame), only taken when the media is not at the target size."""
-        n_frames = media_items.shape[2]
-        if media_items.shape[-2:] != (height, width):
-            flat = media_items.permute(0, 2, 1, 3, 4).flatten(0, 1)
-            flat = torch.nn.functional.interpolate(flat, size=(height, width), mode="bilinear", align_corners=False)
-            media_items = flat.unflatten(0, (-1, n_frames)).permute(0, 2, 1, 3, 4)
-        return media_items
+        """Host pre-processing, only taken when the media is not at the target size."""
+        if tuple(media_items.shape[-2:]) == (height, width):
+            return media_items
+        return _resize_frames(media_items, height, width)
 
     @staticmethod
     def _resize_conditioning_item(item, height, width):                                  # :1550-1563
         if item.media_x or item.media_y:
-            raise ValueError("Provide media_item in the target size for spatial conditioning.")
-        new = copy.copy(item)
-        new.media_item = LTXVideoPipeline.resize_tensor(item.media_item, height, width)
-        return new
+            raise ValueError("ltxmi.LTXVideoPipeline: a conditioning item placed by media_x / media_y is not resized; "
+                             "give its media_item at the size it should have in the frame")
+        resized = copy.copy(item)
+        resized.media_item = LTXVideoPipeline.resize_tensor(item.media_item, height, width)
+        return resized
 
     def _get_latent_spatial_position(self, latents, item, height, width, strip_latent_border):   # :1566-1611
-        scale = self.vae_scale_factor
+        """Where a (possibly smaller) item sits in the frame: (its latents, latent column, latent row).  Centred unless
+        ``media_x`` / ``media_y`` say otherwise."""
+        cell = self.vae_scale_factor
         h, w = item.media_item.shape[-2:]
-        assert h <= height and w <= width, f"Conditioning item size {h}x{w} is larger than target size {height}x{width}"
-        assert h % scale == 0 and w % scale == 0
-        x_start, y_start = item.media_x, item.media_y
-        x_start = (width - w) // 2 if x_start is None else x_start
-        y_start = (height - h) // 2 if y_start is None else y_start
-        if x_start + w > width or y_start + h > height:
-            raise AssertionError(f"Conditioning item {x_start}:{x_start + w}x{y_start}:{y_start + h} is out of bounds for "
-                                 f"target size {width}x{height}")
+        assert h <= height and w <= width, f"a {w}x{h} conditioning item does not fit a {width}x{height} frame"
+        assert h % cell == 0 and w % cell == 0, f"a conditioning item's size is a multiple of {cell}, got {w}x{h}"
+        left = (width - w) // 2 if item.media_x is None else item.media_x
+        top = (height - h) // 2 if item.media_y is None else item.media_y
+        assert left + w <= width and top + h <= height, \
+            f"a {w}x{h} conditioning item at ({left}, {top}) sticks out of the {width}x{height} frame"
         if strip_latent_border:
             # one latent row / column is dropped on every side of the item that does not touch the frame's border
             # (pipeline_ltx_video.py:1598-1611); a cut on the left / top moves the item's origin by one latent
-            cut_l, cut_t = int(x_start > 0), int(y_start > 0)
-            cut_r, cut_b = int(x_start + w < width), int(y_start + h < height)
+            cut_l, cut_t = int(left > 0), int(top > 0)
+            cut_r, cut_b = int(left + w < width), int(top + h < height)
             hl, wl = latents.shape[-2], latents.shape[-1]
             latents = latents[..., cut_t:hl - cut_b, cut_l:wl - cut_r]
-            x_start += cut_l * scale
-            y_start += cut_t * scale
-        return latents, x_start // scale, y_start // scale
+            left += cut_l * cell
+            top += cut_t * cell
+        return latents, left // cell, top // cell
 
     @staticmethod
     def _handle_non_first_conditioning_sequence(init_latents, init_conditioning_mask, latents, media_frame_number,
                                                 strength, num_prefix_latent_frames=2, prefix_latents_mode="concat",
                                                 prefix_soft_conditioning_strength=0.15):           # :1614-1690
-        f_l = latents.shape[2]
-        f_l_p = num_prefix_latent_frames
-        assert f_l >= f_l_p
-        assert media_frame_number % 8 == 0
-        if f_l > f_l_p:
-            s = media_frame_number // 8 + f_l_p
-            e = s + f_l - f_l_p
-            init_latents[:, :, s:e] = torch.lerp(init_latents[:, :, s:e], latents[:, :, f_l_p:], strength)
-            init_conditioning_mask[:, s:e] = strength
+        """A frame sequence that starts inside the video (pixel frame ``media_frame_number`` > 0).  Its latent frames past
+        the first ``num_prefix_latent_frames`` are blended into the grid where they belong.  The prefix is handed back to
+        become extra tokens ("concat"), or blended in too -- all but its first frame, at no more than
+        ``prefix_soft_conditioning_strength`` -- ("soft"), or left out ("drop").  Writes ``init_latents`` and
+        ``init_conditioning_mask`` in place; returns them and the kept prefix (or None)."""
+        if prefix_latents_mode not in ("concat", "soft", "drop"):
+            raise ValueError(f"ltxmi.LTXVideoPipeline: prefix_latents_mode is 'concat', 'soft' or 'drop', not {prefix_latents_mode!r}")
+        num_frames, num_prefix = latents.shape[2], num_prefix_latent_frames
+        assert num_frames >= num_prefix, "the sequence is shorter than its prefix"
+        assert media_frame_number % 8 == 0, "a sequence starts on a latent frame (every 8th pixel frame)"
+        first = media_frame_number // 8                                # the grid's latent frame under the sequence's first
+
+        def blend(begin, end, weight):
+            """The sequence's latent frames [begin, end) into the grid frames under them, and the mask marked."""
+            under = slice(first + begin, first + end)
+            init_latents[:, :, under] = torch.lerp(init_latents[:, :, under], latents[:, :, begin:end], weight)
+            init_conditioning_mask[:, under] = weight
+
+        blend(num_prefix, num_frames, strength)                        # the body
         if prefix_latents_mode == "soft":
-            if f_l_p > 1:
-                s = media_frame_number // 8 + 1
-                e = s + f_l_p - 1
-                strength = min(prefix_soft_conditioning_strength, strength)
-                init_latents[:, :, s:e] = torch.lerp(init_latents[:, :, s:e], latents[:, :, 1:f_l_p], strength)
-                init_conditioning_mask[:, s:e] = strength
-            latents = None
-        elif prefix_latents_mode == "drop":
-            latents = None
-        elif prefix_latents_mode == "concat":
-            latents = latents[:, :, :f_l_p]
-        else:
-            raise ValueError(f"Invalid prefix_latents_mode: {prefix_latents_mode}")
-        return init_latents, init_conditioning_mask, latents
+            blend(1, num_prefix, min(prefix_soft_conditioning_strength, strength))
+        prefix = latents[:, :, :num_prefix] if prefix_latents_mode == "concat" else None
+        return init_latents, init_conditioning_mask, prefix
 
     def _pixel_coords(self, latent_coords, causal_fix=True):
         return latent_to_pixel_coords_from_factors(
@@ -303,54 +282,49 @@ class LTXVideoPipeline:
                              vae_per_channel_normalize=False, generator=None, sample_posterior=True):
         """:1344-1548.  init_latents (b, c, f_l, h_l, w_l) -> (latents (b, N, c), pixel_coords (b, 3, N),
         conditioning_mask (b, N) fp32 or None, number of extra conditioning tokens in front)."""
-        extra_latents, extra_coords, extra_mask, n_extra = [], [], [], 0
+        extra_latents, extra_coords, extra_mask = [], [], []
         causal_fix = bool(getattr(self.transformer.config, "causal_temporal_positioning", True))
-        if conditioning_items:
-            init_mask = torch.zeros(init_latents[:, 0].shape, dtype=torch.float32, device=init_latents.device)
-            for item in conditioning_items:
-                item = self._resize_conditioning_item(item, height, width)
-                media, frame_no, strength = item.media_item, item.media_frame_number, item.conditioning_strength
-                assert media.ndim == 5
-                b, c, n_frames, h, w = media.shape
-                assert (height == h and width == w) or frame_no == 0, \
-                    f"Dimensions do not match: {height}x{width} != {h}x{w} - allowed only when media_frame_number == 0"
-                assert n_frames % 8 == 1
-                assert frame_no >= 0 and frame_no + n_frames <= num_frames
-                lat = vae_encode(media.to(dtype=self.vae.dtype, device=self.vae.device), self.vae,
-                                 vae_per_channel_normalize=vae_per_channel_normalize, generator=generator,
-                                 sample_posterior=sample_posterior).to(dtype=init_latents.dtype)
-                if frame_no == 0:
-                    lat, l_x, l_y = self._get_latent_spatial_position(lat, item, height, width, strip_latent_border=True)
-                    _, _, f_l, h_l, w_l = lat.shape
-                    region = init_latents[:, :, :f_l, l_y:l_y + h_l, l_x:l_x + w_l]
-                    init_latents[:, :, :f_l, l_y:l_y + h_l, l_x:l_x + w_l] = torch.lerp(region, lat, strength)
-                    init_mask[:, :f_l, l_y:l_y + h_l, l_x:l_x + w_l] = strength
-                else:
-                    if n_frames > 1:
-                        init_latents, init_mask, lat = self._handle_non_first_conditioning_sequence(
-                            init_latents, init_mask, lat, frame_no, strength)
-                    if lat is not None:
-                        noise = torch.randn(lat.shape, generator=generator, device=lat.device, dtype=lat.dtype)
-                        lat = torch.lerp(noise, lat, strength)
-                        lat, coords = self.patchifier.patchify(lat)
-                        pc = self._pixel_coords(coords, causal_fix)
-                        pc[:, 0] += frame_no
-                        n_extra += lat.shape[1]
-                        extra_latents.append(lat)
-                        extra_coords.append(pc)
-                        extra_mask.append(torch.full(lat.shape[:2], strength, dtype=torch.float32,
-                                                     device=init_latents.device))
+        init_mask = torch.zeros_like(init_latents[:, 0], dtype=torch.float32) if conditioning_items else None
+        for item in conditioning_items or ():
+            item = self._resize_conditioning_item(item, height, width)
+            media, frame_no, strength = item.media_item, item.media_frame_number, item.conditioning_strength
+            assert media.ndim == 5, "a conditioning item is (b, 3, f, h, w)"
+            n_frames, (h, w) = media.shape[2], media.shape[-2:]
+            assert (h, w) == (height, width) or frame_no == 0, \
+                f"only an item at frame 0 may be smaller than the frame: {w}x{h} in {width}x{height} at frame {frame_no}"
+            assert n_frames % 8 == 1, f"a conditioning item has 8k + 1 frames, got {n_frames}"
+            assert 0 <= frame_no <= num_frames - n_frames, \
+                f"frames {frame_no}..{frame_no + n_frames - 1} of a conditioning item lie outside the {num_frames}-frame video"
+            lat = vae_encode(media.to(dtype=self.vae.dtype, device=self.vae.device), self.vae,
+                             vae_per_channel_normalize=vae_per_channel_normalize, generator=generator,
+                             sample_posterior=sample_posterior).to(dtype=init_latents.dtype)
+            if frame_no == 0:                                          # written into the grid, at its place in the frame
+                lat, x, y = self._get_latent_spatial_position(lat, item, height, width, strip_latent_border=True)
+                f, y1, x1 = lat.shape[2], y + lat.shape[3], x + lat.shape[4]
+                init_latents[:, :, :f, y:y1, x:x1] = torch.lerp(init_latents[:, :, :f, y:y1, x:x1], lat, strength)
+                init_mask[:, :f, y:y1, x:x1] = strength
+                continue
+            if n_frames > 1:
+                init_latents, init_mask, lat = self._handle_non_first_conditioning_sequence(
+                    init_latents, init_mask, lat, frame_no, strength)
+            if lat is not None:                                        # extra tokens in front, at the item's frames
+                noise = torch.randn(lat.shape, generator=generator, device=lat.device, dtype=lat.dtype)
+                tokens, coords = self.patchifier.patchify(torch.lerp(noise, lat, strength))
+                coords = self._pixel_coords(coords, causal_fix)
+                coords[:, 0] += frame_no
+                extra_latents.append(tokens)
+                extra_coords.append(coords)
+                extra_mask.append(torch.full(tokens.shape[:2], strength, dtype=torch.float32, device=init_latents.device))
         latents, coords = self.patchifier.patchify(init_latents)
         pixel_coords = self._pixel_coords(coords, causal_fix)
-        if not conditioning_items:
+        if init_mask is None:
             return latents, pixel_coords, None, 0
-        mask, _ = self.patchifier.patchify(init_mask.unsqueeze(1))
-        mask = mask.squeeze(-1)
+        mask = self.patchifier.patchify(init_mask.unsqueeze(1))[0].squeeze(-1)
         if extra_latents:
             latents = torch.cat([*extra_latents, latents], dim=1)
             pixel_coords = torch.cat([*extra_coords, pixel_coords], dim=2)
             mask = torch.cat([*extra_mask, mask], dim=1)
-        return latents, pixel_coords, mask, n_extra
+        return latents, pixel_coords, mask, sum(x.shape[1] for x in extra_latents)
 
     retrieve_timesteps = staticmethod(retrieve_timesteps)        # (a module-level function in the reference, :125)
 
@@ -381,6 +355,63 @@ class LTXVideoPipeline:
             else:
                 skip_block_list = [skip_block_list[mapping[i]] for i in range(n)]
         return gs, stg, rs, skip_block_list
+
+    @staticmethod
+    def _refuse_outside_this_path(prompt, prompt_embeds, is_video, mixed_precision, offload_to_cpu, num_videos):
+        """What the reference's ``__call__`` takes and this one does not."""
+        _refuse([(refused, NotImplementedError, message) for refused, message in [
+            (prompt is not None or prompt_embeds is None,
+             "__call__ takes prompt_embeds / prompt_attention_mask (as the reference's loop does, :1029-1051); string "
+             "prompts go through encode_prompt / LTXMultiScalePipeline with the caller's T5"),
+            (not is_video, "is_video=False (single images, video_scale_factor 1) is outside this path"),
+            (mixed_precision, "mixed_precision=True (fp32 latents under autocast, :1153-1156) is not on this path"),
+            (offload_to_cpu, "offload_to_cpu is not on this path (everything is resident in HBM)"),
+            (num_videos != 1,
+             "one prompt and one video per call on this path (the reference's CFG-star broadcast at "
+             "pipeline_ltx_video.py:1199 is only well-formed for batch 1)"),
+        ]])
+
+    def _initial_latents(self, latents, media_items, timestep, latent_shape, dtype, device, generator,
+                         vae_per_channel_normalize):
+        """The (b, c, f, h, w) grid the loop starts from (:1056-1065), in fp32 or bf16."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("ltxmi.LTXVideoPipeline: latents are kept in fp32 or bf16 (prompt_embeds' dtype by default)")
+        if latents is not None and latents.dim() == 3:                                   # extension: given patchified noise
+            channels, _, rows, cols = latent_shape[1:]
+            return self.patchifier.unpatchify(latents.to(device=device, dtype=dtype), rows, cols, channels)
+        return self.prepare_latents(latents=latents, media_items=media_items, timestep=timestep, latent_shape=latent_shape,
+                                    dtype=dtype, device=device, generator=generator,
+                                    vae_per_channel_normalize=vae_per_channel_normalize)
+
+    @staticmethod
+    def _stochastic_step_(noise_pred, latents, t, dt, guidance, cond_mask, one_minus_mask):
+        """rf.py:368-373 behind the same guidance: x0 = x - t v by the fused kernel with dt = t on a copy (tokens the mask
+        holds back stay as they are), then the re-noising to t - dt; the draw comes from the global RNG, as the
+        reference's torch.randn_like does.  ``guidance`` = ops.guidance_step_'s arguments after ``dt``."""
+        x0 = latents.clone()
+        ops.guidance_step_(noise_pred, x0, t, *guidance, cond_mask=cond_mask, t=t)
+        t_next = t - dt
+        renoised = (1 - t_next) * x0 + t_next * torch.randn_like(latents)
+        if cond_mask is None:
+            latents.copy_(renoised)
+        else:
+            latents.copy_(torch.where((t - 1e-6 < one_minus_mask).unsqueeze(-1), renoised, latents))
+
+    def _decode(self, latents, output_type, is_video, vae_per_channel_normalize, decode_timestep, decode_noise_scale):
+        """(b, c, f, h, w) latents -> what ``output_type`` asks for (:1270-1299).  A timestep-conditioned decoder gets the
+        latents mixed with fresh noise (global RNG) at ``decode_noise_scale`` (default: ``decode_timestep``), per sample."""
+        if output_type == "latent":
+            return latents
+        timestep = None
+        if self.vae.decoder.timestep_conditioning:
+            def per_sample(value):
+                return torch.tensor(value if isinstance(value, list) else [value] * latents.shape[0]).to(latents.device)
+            timestep = per_sample(decode_timestep)
+            scale = per_sample(decode_timestep if decode_noise_scale is None else decode_noise_scale)[:, None, None, None, None]
+            latents = latents * (1 - scale) + torch.randn_like(latents) * scale
+        image = vae_decode(latents.to(self.vae.dtype), self.vae, is_video,
+                           vae_per_channel_normalize=vae_per_channel_normalize, timestep=timestep)
+        return self.postprocess(image, output_type)
 
     @torch.no_grad()
     def __call__(
@@ -453,106 +484,43 @@ class LTXVideoPipeline:
         computed) -- both bit-identical to the plain loop; ``latents_dtype`` (default = the reference's: the dtype of
         ``prompt_embeds``, :1062); ``sample_conditioning_posterior``; and a (b, N, c) ``latents`` tensor is taken as the
         patchified initial noise as is (the reference rejects 3-D latents)."""
-        tr = self.transformer
         is_video = kwargs.get("is_video", False)
+        per_channel = kwargs.get("vae_per_channel_normalize", True)
+        image_cond_noise_scale = kwargs.get("image_cond_noise_scale", 0.0)
         self.check_inputs(prompt, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds,
                           prompt_attention_mask, negative_prompt_attention_mask, enhance_prompt)
-        if prompt is not None or prompt_embeds is None:
-            raise NotImplementedError("ltxmi.LTXVideoPipeline.__call__ takes prompt_embeds / prompt_attention_mask (as the "
-                                      "reference's loop does, :1029-1051); string prompts go through encode_prompt / "
-                                      "LTXMultiScalePipeline with the caller's T5")
-        if not is_video:
-            raise NotImplementedError("ltxmi: is_video=False (single images, video_scale_factor 1) is outside this path")
-        if mixed_precision:
-            raise NotImplementedError("ltxmi: mixed_precision=True (fp32 latents under autocast, :1153-1156) is not on this path")
-        if offload_to_cpu:
-            raise NotImplementedError("ltxmi: offload_to_cpu is not on this path (everything is resident in HBM)")
-        batch_size = prompt_embeds.shape[0]
-        if batch_size * num_images_per_prompt != 1:
-            raise NotImplementedError("one prompt and one video per call on this path (the reference's CFG-star "
-                                      "broadcast at pipeline_ltx_video.py:1199 is only well-formed for batch 1)")
-        device = self._execution_device
-        vae_per_channel_normalize = kwargs.get("vae_per_channel_normalize", True)
-        image_cond_noise_scale = kwargs.get("image_cond_noise_scale", 0.0)
-        if ltxv_model is None:
-            ltxv_model = self                                                            # holder of ``_interrupt``
+        self._refuse_outside_this_path(prompt, prompt_embeds, is_video, mixed_precision, offload_to_cpu,
+                                       num_images_per_prompt * (0 if prompt_embeds is None else prompt_embeds.shape[0]))
+        tr, device = self.transformer, self._execution_device
+        holder = self if ltxv_model is None else ltxv_model                              # of ``_interrupt``
 
-        latent_height = height // self.vae_scale_factor
-        latent_width = width // self.vae_scale_factor
-        latent_num_frames = num_frames // self.video_scale_factor + 1                    # :921-923
-        C = tr.config.in_channels
-        latent_shape = (batch_size * num_images_per_prompt, C, latent_num_frames, latent_height, latent_width)
-
+        grid = (num_frames // self.video_scale_factor + 1, height // self.vae_scale_factor,
+                width // self.vae_scale_factor)                                          # latent f, h, w  :921-923
+        latent_shape = (1, tr.config.in_channels, *grid)
         assert strength == 1.0 or latents is not None or media_items is not None, \
-            "strength < 1 is used for image-to-image/video-to-video - media_item or latents should be provided."
+            "ltxmi.LTXVideoPipeline: strength < 1 re-noises given content: pass latents or media_items with it"
         timesteps, num_inference_steps = self.retrieve_timesteps(                       # :943-952
             self.scheduler, None if timesteps is not None else num_inference_steps, device, timesteps,
             max_timestep=strength, skip_initial_inference_steps=skip_initial_inference_steps,
             skip_final_inference_steps=skip_final_inference_steps, samples_shape=latent_shape)
         if self.allowed_inference_steps is not None:                                     # :953-957
-            for t in [round(x, 4) for x in timesteps]:
-                assert t in self.allowed_inference_steps, \
-                    f"Invalid inference timestep {t}. Allowed timesteps are {self.allowed_inference_steps}."
+            outside = [t for t in timesteps if round(t, 4) not in self.allowed_inference_steps]
+            assert not outside, f"ltxmi.LTXVideoPipeline: timesteps {outside} are not among {self.allowed_inference_steps}"
+        plan = _StepPlan(tr, timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list, guidance_timesteps,
+                         (prompt_embeds, prompt_attention_mask), (negative_prompt_embeds, negative_prompt_attention_mask),
+                         device, dead_row_elimination, stg_row_dedup and joint_pass)
 
-        gs_tab, stg_tab, rs_tab, skip_tab = self._guidance_tables(                      # :959-1013
-            timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list, guidance_timesteps)
-        do_cfg = any(x > 1.0 for x in gs_tab)
-        do_stg = any(x > 0.0 for x in stg_tab)
-        do_rescale = any(x != 1.0 for x in rs_tab)
-
-        # Rows of the batch per step.  The reference keeps num_conds constant and zeroes the scales of the
-        # steps that should not use a guidance (:980-983); a row whose scale is zero at a step does not reach
-        # that step's result (:1183-1222), so it is not computed here (``dead_row_elimination``; bit-identical:
-        # every kernel computes a row independently of the others).
-        def rows_for(i):
-            if not dead_row_elimination:
-                return do_cfg, do_stg
-            return (do_cfg and gs_tab[i] > 1.0), (do_stg and stg_tab[i] > 0.0)
-
-        batches = {}                             # (use_cfg, use_stg) -> (embeds, mask, num_conds)  :1035-1051
-
-        def batch_for(use_cfg, use_stg):
-            key = (use_cfg, use_stg)
-            if key not in batches:
-                e, m = prompt_embeds, prompt_attention_mask.to(device)
-                if use_cfg:
-                    e = torch.cat([negative_prompt_embeds, e], dim=0)
-                    m = torch.cat([negative_prompt_attention_mask.to(device), m], dim=0)
-                if use_stg:
-                    e = torch.cat([e, prompt_embeds], dim=0)
-                    m = torch.cat([m, prompt_attention_mask.to(device)], dim=0)
-                batches[key] = (e.to(device=device, dtype=tr.dtype), m, 1 + int(use_cfg) + int(use_stg))
-            return batches[key]
-
-        mask_cache = {}
-
-        def skip_mask_for(i, use_stg, nconds):                                           # :1016-1026
-            if not use_stg or skip_tab is None:
-                return None
-            key = (tuple(skip_tab[i]), nconds)
-            if key not in mask_cache:
-                mask_cache[key] = tr.create_skip_layer_mask(batch_size, nconds, nconds - 1, list(skip_tab[i]))
-            return mask_cache[key]
-
-        if latents_dtype is None:
-            latents_dtype = prompt_embeds.dtype                                          # :1062 (mixed_precision is refused)
-        if latents_dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError("ltxmi.LTXVideoPipeline: latents are kept in fp32 or bf16 (prompt_embeds' dtype by default)")
-        if latents is not None and latents.dim() == 3:                                   # extension: given patchified noise
-            grid5 = self.patchifier.unpatchify(latents.to(device=device, dtype=latents_dtype), latent_height, latent_width, C)
-        else:                                                                            # prepare_latents :1056-1065
-            grid5 = self.prepare_latents(latents=latents, media_items=media_items, timestep=timesteps[0],
-                                         latent_shape=latent_shape, dtype=latents_dtype, device=device, generator=generator,
-                                         vae_per_channel_normalize=vae_per_channel_normalize)
-
+        start = self._initial_latents(latents, media_items, timesteps[0], latent_shape,
+                                      prompt_embeds.dtype if latents_dtype is None else latents_dtype,    # :1062
+                                      device, generator, per_channel)
         # conditioning items -> latents / coords / mask (+ extra tokens in front)           :1067-1085
         latents, pixel_coords, cond_mask, num_cond_latents = self.prepare_conditioning(
-            conditioning_items, grid5.contiguous(), num_frames, height, width, vae_per_channel_normalize, generator,
+            conditioning_items, start.contiguous(), num_frames, height, width, per_channel, generator,
             sample_posterior=sample_conditioning_posterior)
         latents = latents.contiguous()
-        init_latents = latents.clone() if cond_mask is not None else None
+        init_latents = one_minus_mask = None
         if cond_mask is not None:
-            cond_mask = cond_mask.contiguous()
+            init_latents, cond_mask = latents.clone(), cond_mask.contiguous()
             one_minus_mask = 1.0 - cond_mask
         frac = pixel_coords.to(torch.float32)
         frac[:, 0] = frac[:, 0] * (1.0 / frame_rate)                                     # :1086-1087
@@ -569,72 +537,94 @@ class LTXVideoPipeline:
             if cond_mask is not None and image_cond_noise_scale > 0.0:                   # :1105-1113
                 noise = torch.randn(latents.shape, generator=generator, device=device, dtype=latents.dtype)
                 ops.image_cond_noise_(latents, init_latents, noise, cond_mask, image_cond_noise_scale, t)
-            use_cfg, use_stg = rows_for(i)
-            embeds, mask, nconds = batch_for(use_cfg, use_stg)
+            use_cfg, use_stg = plan.rows(i)
+            embeds, mask, nconds = plan.batch(use_cfg, use_stg)
             model_in = latents.to(tr.dtype)
             if nconds > 1:
                 model_in = model_in.expand(nconds, -1, -1)
             current_timestep = t_dev[i].expand(nconds).unsqueeze(-1)                     # [B_eff, 1]
             if cond_mask is not None:                                                    # :1145-1150, [B_eff, N]
                 current_timestep = torch.minimum(current_timestep, one_minus_mask.expand(nconds, -1))
-            alias = 0
-            if stg_row_dedup and use_stg and joint_pass:
-                blocks = skip_tab[i] if skip_tab is not None else []
-                alias = min(blocks) if len(blocks) > 0 else len(tr.transformer_blocks)
             noise_pred = tr(model_in, freqs_cis=freqs_cis, encoder_hidden_states=embeds,
-                            encoder_attention_mask=mask, timestep=current_timestep, stg_alias_blocks=alias,
-                            skip_layer_mask=skip_mask_for(i, use_stg, nconds),
-                            skip_layer_strategy=skip_layer_strategy, latent_shape=latent_shape[2:], joint_pass=joint_pass,
-                            ltxv_model=ltxv_model, mixed=mixed_precision, return_dict=False)[0]
+                            encoder_attention_mask=mask, timestep=current_timestep,
+                            stg_alias_blocks=plan.stg_alias_blocks(i, use_stg),
+                            skip_layer_mask=plan.skip_mask(i, use_stg, nconds),
+                            skip_layer_strategy=skip_layer_strategy, latent_shape=grid, joint_pass=joint_pass,
+                            ltxv_model=holder, mixed=mixed_precision, return_dict=False)[0]
             if noise_pred is None:                                                       # :1180-1181
                 return None
             dt = self.scheduler.host_dt(t)
-            if not stochastic_sampling:
-                ops.guidance_step_(noise_pred, latents, dt, gs_tab[i], stg_tab[i], rs_tab[i],
-                                   use_cfg, use_stg, do_rescale, workspace, cond_mask=cond_mask, t=t)   # :1183-1241, 1309-1342
+            guidance = (plan.gs[i], plan.stg[i], plan.rs[i], use_cfg, use_stg, plan.do_rescale, workspace)
+            if stochastic_sampling:
+                self._stochastic_step_(noise_pred, latents, t, dt, guidance, cond_mask, one_minus_mask)
             else:
-                # rf.py:368-373 behind the same guidance: x0 = x - t v by the fused kernel with dt = t on a copy (tokens
-                # the mask holds back stay as they are), then the re-noising to t - dt; the draw comes from the global
-                # RNG, as the reference's torch.randn_like does
-                x0 = latents.clone()
-                ops.guidance_step_(noise_pred, x0, t, gs_tab[i], stg_tab[i], rs_tab[i],
-                                   use_cfg, use_stg, do_rescale, workspace, cond_mask=cond_mask, t=t)
-                t_next = t - dt
-                renoised = (1 - t_next) * x0 + t_next * torch.randn_like(latents)
-                if cond_mask is None:
-                    latents.copy_(renoised)
-                else:
-                    latents.copy_(torch.where((t - 1e-6 < one_minus_mask).unsqueeze(-1), renoised, latents))
+                ops.guidance_step_(noise_pred, latents, dt, *guidance, cond_mask=cond_mask, t=t)   # :1183-1241, 1309-1342
             if callback is not None:                                                     # :1243-1247
                 preview = latents[:, num_cond_latents:].squeeze(0).transpose(0, 1)
-                callback(i, preview.reshape(preview.shape[0], latent_num_frames, latent_height, latent_width), False,
-                         pass_no=pass_no)
+                callback(i, preview.reshape(preview.shape[0], *grid), False, pass_no=pass_no)
             if callback_on_step_end is not None:
                 callback_on_step_end(self, i, t, {})
 
-        latents = latents[:, num_cond_latents:]                                          # :1258-1259
-        latents = self.patchifier.unpatchify(latents, latent_height, latent_width, C)    # :1262-1268
-        if output_type != "latent":
-            ts = None
-            if self.vae.decoder.timestep_conditioning:                                   # :1270-1288
-                noise = torch.randn_like(latents)
-                if not isinstance(decode_timestep, list):
-                    decode_timestep = [decode_timestep] * latents.shape[0]
-                if decode_noise_scale is None:
-                    decode_noise_scale = decode_timestep
-                elif not isinstance(decode_noise_scale, list):
-                    decode_noise_scale = [decode_noise_scale] * latents.shape[0]
-                ts = torch.tensor(decode_timestep).to(latents.device)
-                scale = torch.tensor(decode_noise_scale).to(latents.device)[:, None, None, None, None]
-                latents = latents * (1 - scale) + noise * scale
-            image = vae_decode(latents.to(self.vae.dtype), self.vae, is_video,
-                               vae_per_channel_normalize=vae_per_channel_normalize, timestep=ts)
-            image = self.postprocess(image, output_type)
-        else:
-            image = latents
-        if not return_dict:
-            return (image,)
-        return image                                                                     # :1306: the bare tensor
+        latents = self.patchifier.unpatchify(latents[:, num_cond_latents:], grid[1], grid[2], latent_shape[1])   # :1258-1268
+        image = self._decode(latents, output_type, is_video, per_channel, decode_timestep, decode_noise_scale)
+        return image if return_dict else (image,)                                        # :1306: the bare tensor
+
+
+class _StepPlan:
+    """Which rows of the batch each step of the loop runs, and on what: decided on the host, once, from the per-step
+    tables.  The row batches and the skip-layer masks are built when a step first needs them and then kept."""
+
+    def __init__(self, transformer, timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list,
+                 guidance_timesteps, positive, negative, device, dead_row_elimination, stg_row_dedup):
+        self.gs, self.stg, self.rs, self.skip = LTXVideoPipeline._guidance_tables(        # :959-1013
+            timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list, guidance_timesteps)
+        self.do_cfg = any(x > 1.0 for x in self.gs)
+        self.do_stg = any(x > 0.0 for x in self.stg)
+        self.do_rescale = any(x != 1.0 for x in self.rs)
+        self.transformer, self.device = transformer, device
+        self.positive, self.negative = positive, negative
+        self.dead_row_elimination, self.stg_row_dedup = dead_row_elimination, stg_row_dedup
+        self._batches, self._skip_masks = {}, {}
+
+    def rows(self, i):
+        """(negative row?, STG row?) of step ``i``.  The reference keeps num_conds constant and zeroes the scales of the
+        steps that should not use a guidance (:980-983); a row whose scale is zero at a step does not reach that step's
+        result (:1183-1222), so it is not computed here (``dead_row_elimination``; bit-identical: every kernel computes
+        a row independently of the others)."""
+        if not self.dead_row_elimination:
+            return self.do_cfg, self.do_stg
+        return (self.do_cfg and self.gs[i] > 1.0), (self.do_stg and self.stg[i] > 0.0)
+
+    def batch(self, use_cfg, use_stg):
+        """(embeds, mask, number of rows) in the order negative, positive, STG (= positive again)  :1035-1051."""
+        key = (use_cfg, use_stg)
+        if key not in self._batches:
+            (e, m), (negative_e, negative_m) = self.positive, self.negative
+            m = m.to(self.device)
+            if use_cfg:
+                e = torch.cat([negative_e, e], dim=0)
+                m = torch.cat([negative_m.to(self.device), m], dim=0)
+            if use_stg:
+                e = torch.cat([e, self.positive[0]], dim=0)
+                m = torch.cat([m, self.positive[1].to(self.device)], dim=0)
+            self._batches[key] = (e.to(device=self.device, dtype=self.transformer.dtype), m, e.shape[0])
+        return self._batches[key]
+
+    def skip_mask(self, i, use_stg, nconds):                                             # :1016-1026
+        if not use_stg or self.skip is None:
+            return None
+        key = (tuple(self.skip[i]), nconds)
+        if key not in self._skip_masks:
+            self._skip_masks[key] = self.transformer.create_skip_layer_mask(1, nconds, nconds - 1, list(self.skip[i]))
+        return self._skip_masks[key]
+
+    def stg_alias_blocks(self, i, use_stg):
+        """How many leading blocks the STG row shares with the positive row at step ``i`` (``stg_row_dedup``): all up to
+        the step's first skipped block."""
+        if not (self.stg_row_dedup and use_stg):
+            return 0
+        blocks = self.skip[i] if self.skip is not None else []
+        return min(blocks) if len(blocks) > 0 else len(self.transformer.transformer_blocks)
 
 
 class LTXMultiScalePipeline:
@@ -644,27 +634,27 @@ class LTXMultiScalePipeline:
     ``video_pipeline.encode_prompt`` with the caller's T5; everything else travels in ``**kwargs``."""
 
     def __init__(self, video_pipeline: LTXVideoPipeline, latent_upsampler):
-        self.video_pipeline = video_pipeline
+        self.video_pipeline, self.latent_upsampler = video_pipeline, latent_upsampler
         self.vae = video_pipeline.vae
-        self.latent_upsampler = latent_upsampler
 
     def _upsample_latents(self, latest_upsampler, latents):                              # :1760-1772
         from .latent_upsampler import upsample_latents
         return upsample_latents(latest_upsampler, latents, self.vae)
 
+    def _run_pass(self, number, args, shared, overrides, **fixed):
+        """One pass of the video pipeline: the shared arguments, then what the pass fixes, then the caller's
+        ``first_pass`` / ``second_pass`` overrides; ``num_inference_steps<number>`` names the pass's step count."""
+        call = {**shared, **fixed, "pass_no": number, **overrides}
+        if f"num_inference_steps{number}" in call:                                       # :1862 (required there)
+            call["num_inference_steps"] = call[f"num_inference_steps{number}"]
+        return self.video_pipeline(*args, **call)
+
     def __call__(self, downscale_factor: float, first_pass: dict, second_pass: dict, *args: Any, **kwargs: Any) -> Any:
         from .latent_upsampler import adain_filter_latent
         vp = self.video_pipeline
-        original_output_type = kwargs["output_type"]
-        original_width, original_height = kwargs["width"], kwargs["height"]
-        x_width = int(kwargs["width"] * downscale_factor)                                # :1797-1800
-        downscaled_width = x_width - (x_width % vp.vae_scale_factor)
-        x_height = int(kwargs["height"] * downscale_factor)
-        downscaled_height = x_height - (x_height % vp.vae_scale_factor)
-        kwargs["output_type"] = "latent"
-        kwargs["width"] = downscaled_width
-        kwargs["height"] = downscaled_height
-
+        output_type, (height, width) = kwargs["output_type"], (kwargs["height"], kwargs["width"])
+        small_height, small_width = (int(x * downscale_factor) // vp.vae_scale_factor * vp.vae_scale_factor
+                                     for x in (height, width))                           # :1797-1800
         # extension: VAE_tile_size / ltxv_model / device / prompt may be absent (the reference raises KeyError)
         z_tile, hw_tile = kwargs.get("VAE_tile_size") or (0, 0)                          # :1806-1814
         if z_tile > 0:
@@ -673,46 +663,22 @@ class LTXMultiScalePipeline:
             self.vae.enable_hw_tiling()
             self.vae.set_tiling_params(hw_tile)
 
-        ltxv_model = kwargs.get("ltxv_model")
-        prompt = kwargs.pop("prompt", None)
-        negative_prompt = kwargs.pop("negative_prompt", None)
-        if prompt is not None or kwargs.get("prompt_embeds") is None:                    # :1833-1852
-            (kwargs["prompt_embeds"], kwargs["prompt_attention_mask"], kwargs["negative_prompt_embeds"],
-             kwargs["negative_prompt_attention_mask"]) = vp.encode_prompt(
-                prompt, True, negative_prompt=negative_prompt, device=kwargs.get("device"), text_encoder_max_tokens=256)
-        if ltxv_model is not None and ltxv_model._interrupt:
+        shared = {k: v for k, v in kwargs.items() if k not in ("prompt", "negative_prompt")}
+        if kwargs.get("prompt") is not None or shared.get("prompt_embeds") is None:     # :1833-1852
+            names = ("prompt_embeds", "prompt_attention_mask", "negative_prompt_embeds", "negative_prompt_attention_mask")
+            shared.update(zip(names, vp.encode_prompt(kwargs.get("prompt"), True, negative_prompt=kwargs.get("negative_prompt"),
+                                                      device=shared.get("device"), text_encoder_max_tokens=256)))
+        if getattr(shared.get("ltxv_model"), "_interrupt", False):
             return None
-        original_kwargs = kwargs.copy()
 
-        kwargs["joint_pass"] = True
-        kwargs["pass_no"] = 1
-        kwargs.update(**first_pass)
-        if "num_inference_steps1" in kwargs:                                             # :1862 (required there)
-            kwargs["num_inference_steps"] = kwargs["num_inference_steps1"]
-        latents = vp(*args, **kwargs)
+        latents = self._run_pass(1, args, shared, first_pass, output_type="latent", height=small_height,
+                                 width=small_width, joint_pass=True)
         if latents is None:
             return None
-
         upsampled = self._upsample_latents(self.latent_upsampler, latents)               # :1869-1873
         upsampled = adain_filter_latent(latents=upsampled, reference_latents=latents)
-
-        kwargs = original_kwargs
-        kwargs["latents"] = upsampled
-        kwargs["output_type"] = original_output_type
-        kwargs["width"] = downscaled_width * 2
-        kwargs["height"] = downscaled_height * 2
-        kwargs["joint_pass"] = False
-        kwargs["pass_no"] = 2
-        kwargs.update(**second_pass)
-        if "num_inference_steps2" in kwargs:
-            kwargs["num_inference_steps"] = kwargs["num_inference_steps2"]
-        result = vp(*args, **kwargs)
-        if result is None:
-            return None
-        if original_output_type != "latent":                                             # :1891-1903 (host post-processing)
-            num_frames = result.shape[2]
-            videos = result.permute(0, 2, 1, 3, 4).flatten(0, 1)
-            videos = torch.nn.functional.interpolate(videos, size=(original_height, original_width), mode="bilinear",
-                                                     align_corners=False)
-            result = videos.unflatten(0, (-1, num_frames)).permute(0, 2, 1, 3, 4)
-        return result
+        result = self._run_pass(2, args, shared, second_pass, latents=upsampled, output_type=output_type,
+                                height=small_height * 2, width=small_width * 2, joint_pass=False)
+        if result is None or output_type == "latent":
+            return result
+        return _resize_frames(result, height, width)                                     # :1891-1903 (host post-processing)

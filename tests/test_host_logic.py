@@ -1,6 +1,7 @@
 """Host-side logic of the PRODUCT (ltxmi/) against the reference-generated golden vectors -- CPU only.
 RoPE tables, the scheduler, the per-step guidance tables and the skip-layer masks are computed on the host once
 per generation; none of them needs a GPU, so they are pinned here directly (not only through model-level tolerances)."""
+import pytest
 import torch
 
 import ltxmi
@@ -276,3 +277,205 @@ def test_entry_point_signatures_match_the_reference():
     # is out of scope): the names are reused for the LTX DiT, INTEGRATION.md says so -- keep that statement honest
     from ltxmi import distributed as sp
     assert [p["name"] for p in _sig(sp.usp_dit_forward)][:2] != [p["name"] for p in ref["wan.usp_dit_forward"]][:2]
+
+
+# ------------------------------------------------------------------ the pipeline's prompt and conditioning glue (CPU)
+# LTXVideoPipeline's host code is plain torch on small tensors: pinned here without the library, against the goldens the
+# reference's own methods produced (G12, G15) and against the oracle where no golden exists.
+def _prompt_pipeline(golden):
+    from golden_cases import g15_case
+    t, meta, _, _, _, tok, enc = g15_case(golden)
+    return ltxmi.LTXVideoPipeline(tokenizer=tok, text_encoder=enc), t, meta["call"]
+
+
+def test_g15_product_encode_prompt(golden):
+    """encode_prompt called the way LTXMultiScalePipeline.__call__ calls it, against the tensors the reference's own
+    encode_prompt produced under the same fake T5 (G15)."""
+    pipe, t, call = _prompt_pipeline(golden)
+    with torch.no_grad():
+        got = pipe.encode_prompt(call["prompt"], True, negative_prompt=call["negative_prompt"], device="cpu",
+                                 text_encoder_max_tokens=256)
+    pos, pos_mask, neg, neg_mask = got
+    assert pos.dtype == neg.dtype == pipe.text_encoder.dtype
+    assert torch.equal(pos, t["prompt_embeds"]) and torch.equal(neg, t["negative_prompt_embeds"])
+    assert torch.equal(pos_mask.float(), t["prompt_attention_mask"])
+    assert torch.equal(neg_mask.float(), t["negative_prompt_attention_mask"])
+    assert all(str(x.device) == "cpu" for x in got)
+
+
+def test_encode_prompt_batches_repeats_and_refusals(golden):
+    """Two prompts x two videos per prompt: rows come out prompt-major (p0, p0, p1, p1), the negative prompt is encoded once
+    per prompt at the positive pair's token length, texts are stripped before tokenising (the mask sums are the byte counts
+    + EOS of the STRIPPED texts).  The literals are what the parent commit returns."""
+    pipe, _, _ = _prompt_pipeline(golden)
+    with torch.no_grad():
+        pos, pos_mask, neg, neg_mask = pipe.encode_prompt(["a cat ", "two dogs"], True, negative_prompt=" bad",
+                                                          num_images_per_prompt=2, device="cpu", text_encoder_max_tokens=32)
+    assert pos.shape == neg.shape == (4, 32, 128) and pos_mask.shape == neg_mask.shape == (4, 32)
+    assert pos.dtype == neg.dtype == torch.float32 and pos_mask.dtype == neg_mask.dtype == torch.int64
+    assert torch.equal(pos[0], pos[1]) and torch.equal(pos[2], pos[3]) and not torch.equal(pos[0], pos[2])
+    assert all(torch.equal(neg[0], neg[i]) for i in (1, 2, 3))
+    assert pos_mask.sum(1).tolist() == [6, 6, 9, 9] and neg_mask.sum(1).tolist() == [4, 4, 4, 4]
+    with torch.no_grad():
+        one = pipe.encode_prompt("two dogs", True, negative_prompt="bad", device="cpu", text_encoder_max_tokens=32)
+        assert torch.equal(one[0][0], pos[2]) and torch.equal(one[1][0], pos_mask[2])
+        assert torch.equal(one[2][0], neg[0]) and torch.equal(one[3][0], neg_mask[0])
+        # no guidance: no negative pair, and the negative prompt is not encoded
+        a, b, c, d = pipe.encode_prompt("two dogs", False, device="cpu", text_encoder_max_tokens=32)
+    assert torch.equal(a, one[0]) and torch.equal(b, one[1]) and c is None and d is None
+
+    # given embeddings, no T5: taken as they are, cast to the transformer's dtype (there is no text encoder), repeated per video
+    bare = ltxmi.LTXVideoPipeline()
+    a, b, c, d = bare.encode_prompt(None, True, num_images_per_prompt=2, device="cpu", prompt_embeds=pos[2:3],
+                                    prompt_attention_mask=pos_mask[2:3], negative_prompt_embeds=neg[:1],
+                                    negative_prompt_attention_mask=neg_mask[:1])
+    assert torch.equal(a, pos[2:]) and torch.equal(b, pos_mask[2:]) and torch.equal(c, neg[:2]) and torch.equal(d, neg_mask[:2])
+    import types
+    bf16 = ltxmi.LTXVideoPipeline(transformer=types.SimpleNamespace(dtype=torch.bfloat16, device="cpu"))
+    a, b, c, d = bf16.encode_prompt(None, False, prompt_embeds=pos[:1], prompt_attention_mask=pos_mask[:1])
+    assert torch.equal(a, pos[:1].to(torch.bfloat16)) and torch.equal(b, pos_mask[:1]) and c is None and d is None
+
+    with pytest.raises(RuntimeError):
+        bare.encode_prompt("two dogs", False, device="cpu")
+    with pytest.raises(RuntimeError):           # the positive pair is given, the negative prompt still needs the T5
+        bare.encode_prompt(None, True, negative_prompt="bad", device="cpu", prompt_embeds=pos[:1],
+                           prompt_attention_mask=pos_mask[:1])
+
+
+def _check_inputs_rows():
+    e, m = torch.zeros(1, 4, 8), torch.ones(1, 4)
+    e2, m2 = torch.zeros(1, 5, 8), torch.ones(1, 5)
+    ok = dict(prompt="p", height=64, width=96, negative_prompt=None)
+    emb = dict(ok, prompt=None, prompt_embeds=e, prompt_attention_mask=m)
+    both = dict(emb, negative_prompt_embeds=e, negative_prompt_attention_mask=m)
+    return [
+        # (arguments, exception or None, parameter names the message has to mention)
+        (dict(ok, height=60), ValueError, ["height", "width"]),
+        (dict(ok, width=100), ValueError, ["height", "width"]),
+        (dict(ok, prompt_embeds=e, prompt_attention_mask=m), ValueError, ["prompt", "prompt_embeds"]),
+        (dict(ok, prompt=None), ValueError, ["prompt", "prompt_embeds"]),
+        (dict(ok, prompt=3), ValueError, ["prompt"]),
+        (dict(ok, negative_prompt_embeds=e, negative_prompt_attention_mask=m), ValueError, ["prompt", "negative_prompt_embeds"]),
+        (dict(both, negative_prompt="n"), ValueError, ["negative_prompt", "negative_prompt_embeds"]),
+        (dict(emb, prompt_attention_mask=None), ValueError, ["prompt_attention_mask", "prompt_embeds"]),
+        (dict(both, negative_prompt_attention_mask=None), ValueError,
+         ["negative_prompt_attention_mask", "negative_prompt_embeds"]),
+        (dict(both, negative_prompt_embeds=e2, negative_prompt_attention_mask=m2), ValueError,
+         ["prompt_embeds", "negative_prompt_embeds"]),
+        (dict(both, negative_prompt_attention_mask=m2), ValueError,
+         ["prompt_attention_mask", "negative_prompt_attention_mask"]),
+        (dict(ok, enhance_prompt=True), NotImplementedError, ["enhance_prompt"]),
+        (dict(ok, negative_prompt="n"), None, []),
+        (dict(both), None, []),
+    ]
+
+
+@pytest.mark.parametrize("kwargs,exc,names", _check_inputs_rows())
+def test_check_inputs_refusals(kwargs, exc, names):
+    """One row per refusal of check_inputs (ten ValueErrors, the first listed for height and for width; one
+    NotImplementedError) and two accepted argument sets: the exception type, and that the message names what is wrong."""
+    pipe = ltxmi.LTXVideoPipeline()
+    if exc is None:
+        assert pipe.check_inputs(**kwargs) is None
+        return
+    with pytest.raises(exc) as info:
+        pipe.check_inputs(**kwargs)
+    assert type(info.value) is exc
+    for name in names:
+        assert name in str(info.value), (name, str(info.value))
+
+
+def test_g12_product_latent_spatial_position(golden):
+    """_get_latent_spatial_position against G12: a 64x64 item at x = 32 of a 160x128 frame, vertically centred, touches no
+    border, so one latent row / column goes on every side and the origin moves by one latent."""
+    import types
+    t, meta = golden("g12_conditioning")
+    stub = types.SimpleNamespace(vae_scale_factor=32)
+    item = ltxmi.ConditioningItem(torch.zeros(1, 3, 1, 64, 64), 0, 1.0, media_x=32, media_y=None)
+    out, lx, ly = ltxmi.LTXVideoPipeline._get_latent_spatial_position(stub, t["place.in"], item, 128, 160, True)
+    assert [lx, ly] == meta["place"] and torch.equal(out, t["place.out"])
+    out, lx, ly = ltxmi.LTXVideoPipeline._get_latent_spatial_position(stub, t["place.in"], item, 128, 160, False)
+    assert (lx, ly) == (1, 1) and torch.equal(out, t["place.in"])
+
+
+@pytest.mark.parametrize("mode", ["concat", "soft", "drop", "bogus"])
+@pytest.mark.parametrize("f_l,prefix", [(2, 2), (4, 2), (3, 1), (1, 1), (5, 3)])
+def test_non_first_conditioning_sequence_matches_oracle(mode, f_l, prefix):
+    """A frame sequence that does not start the video: its latent frames past the prefix are blended into the grid, the
+    prefix is kept as extra tokens ("concat"), blended softly ("soft") or dropped.  Against the oracle's restatement; its
+    "concat" path is pinned to the reference by G12 (test_g12_conditioning), "soft" and "drop" have no golden."""
+    from oracle import conditioning as oc
+    g = torch.Generator().manual_seed(100 * f_l + prefix)
+    grid, lat = torch.randn(1, 8, 9, 2, 3, generator=g), torch.randn(1, 8, f_l, 2, 3, generator=g)
+    mask = torch.rand(1, 9, 2, 3, generator=g)
+    args = dict(num_prefix_latent_frames=prefix, prefix_latents_mode=mode, prefix_soft_conditioning_strength=0.15)
+    ours = ltxmi.LTXVideoPipeline._handle_non_first_conditioning_sequence
+    for strength in (0.9, 0.1):                 # 0.1: below the soft prefix strength, which is then capped by it
+        if mode == "bogus":
+            with pytest.raises(ValueError):
+                ours(grid.clone(), mask.clone(), lat.clone(), 16, strength, **args)
+            continue
+        want = oc.handle_non_first_conditioning_sequence(grid.clone(), mask.clone(), lat.clone(), 16, strength, **args)
+        mine_grid, mine_mask = grid.clone(), mask.clone()
+        got = ours(mine_grid, mine_mask, lat.clone(), 16, strength, **args)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+        assert torch.equal(mine_grid, want[0]) and torch.equal(mine_mask, want[1])          # written in place
+        assert (got[2] is None and want[2] is None) or torch.equal(got[2], want[2])
+        assert (got[2] is None) == (mode != "concat")
+        assert torch.equal(mine_grid, grid) == (f_l == prefix and (mode != "soft" or prefix == 1))     # something was written
+
+
+class _TorchWithRecordedDraws:
+    """``torch`` as ltxmi.pipeline sees it, with ``randn`` handing out recorded draws in order."""
+
+    def __init__(self, draws):
+        self.draws, self.used = draws, 0
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+    def randn(self, shape, **kwargs):
+        draw = self.draws[self.used]
+        assert tuple(shape) == tuple(draw.shape), (self.used, tuple(shape), tuple(draw.shape))
+        self.used += 1
+        return draw.clone()
+
+
+def test_g12_product_prepare_conditioning(golden, monkeypatch):
+    """prepare_conditioning end to end on the CPU against what the reference's own method returned (G12): a first-frame
+    image, a 17-frame sequence at frame 8 (its two prefix latent frames become extra tokens) and a single frame at 24.
+    The encoder is the oracle's on G11-b's weights (pinned to the reference by G11), the noise is the recorded draws."""
+    import types
+    from golden_cases import sub
+    from ltxmi import pipeline as pl
+    from oracle import vae_encoder as ve
+    t, meta = golden("g12_conditioning")
+    tb, _ = golden("g11_encoder_b")
+    cfg, sd = meta["cfg"], sub(tb, "sd.")
+    assert torch.equal(sd["encoder.conv_out.conv.weight"], t["weights_check"])
+    sd["per_channel_statistics.std-of-means"] = t["per_channel_statistics.std-of-means"]
+    sd["per_channel_statistics.mean-of-means"] = t["per_channel_statistics.mean-of-means"]
+    vae = types.SimpleNamespace(dtype=torch.float32, device=torch.device("cpu"))
+    pipe = ltxmi.LTXVideoPipeline(
+        vae=vae, transformer=types.SimpleNamespace(config=types.SimpleNamespace(causal_temporal_positioning=True)))
+    encoded = []
+
+    def encode(media, the_vae, **kwargs):
+        assert the_vae is vae and kwargs["vae_per_channel_normalize"] is True
+        encoded.append(tuple(media.shape))
+        return ve.vae_encode(sd, cfg, media)
+
+    fake_torch = _TorchWithRecordedDraws([t[f"noise.{i}"] for i in range(meta["n_prepare_draws"])])
+    monkeypatch.setattr(pl, "vae_encode", encode)
+    monkeypatch.setattr(pl, "torch", fake_torch)
+    items = [ltxmi.ConditioningItem(t["img"], 0, 1.0), ltxmi.ConditioningItem(t["seq"], 8, 0.9),
+             ltxmi.ConditioningItem(t["single"], 24, 0.7)]
+    lat, pc, mask, n_extra = pipe.prepare_conditioning(items, t["init_latents"].clone(), meta["F"], meta["H"], meta["W"],
+                                                       vae_per_channel_normalize=True)
+    assert n_extra == meta["n_extra"] and fake_torch.used == meta["n_prepare_draws"]
+    assert encoded == [tuple(t[k].shape) for k in ("img", "seq", "single")]
+    torch.testing.assert_close(lat, t["latents"], rtol=1e-4, atol=1e-5)
+    assert torch.equal(pc, t["pixel_coords"]) and torch.equal(mask, t["mask"])
+    lat0, pc0, mask0, n0 = pipe.prepare_conditioning(None, t["init_latents"].clone(), meta["F"], meta["H"], meta["W"])
+    assert mask0 is None and n0 == 0 and fake_torch.used == meta["n_prepare_draws"]
+    assert torch.equal(lat0, t["plain.latents"]) and torch.equal(pc0, t["plain.pixel_coords"])

@@ -2,13 +2,10 @@
 own code (oracle/gen/make_golden.py, run in the build container).  CPU only."""
 import torch
 
+from golden_cases import g15_case, sub
 from oracle import dit, vae, sched
 
 TOL = dict(rtol=1e-5, atol=2e-6)   # fp32 vs fp32, different op order in a few places
-
-
-def sub(t, prefix):
-    return {k[len(prefix):]: v for k, v in t.items() if k.startswith(prefix)}
 
 
 def test_g1_g2_rope(golden):
@@ -436,27 +433,6 @@ def test_g0_timestep_embedding(golden):
                        t["emb_256_flip_shift0"])
     assert torch.equal(leaves.get_timestep_embedding(ts, 64), t["emb_64_defaults"])
     assert torch.equal(leaves.get_timestep_embedding(ts, 33, False, 1, 2.0, 1000), t["emb_33_odd_scale2"])
-
-
-def g15_case(golden):
-    """Everything the G15 replay needs, rebuilt from the manifest: the DiT weights are G7's, the VAE decoder and the latent
-    upsampler come from the oracle's seeded initialisers (fingerprints checked, so an RNG drift fails loudly here and not
-    as a parity miss), the prompts go through the same fake T5 as in the generator."""
-    from oracle import upsampler as ou, vae as ov
-    from fake_t5 import FakeTextEncoder, FakeTokenizer
-    t, meta = golden("g15_multiscale_call")
-    w, _ = golden("g7_pipeline_call")
-    sd = sub(w, "w.")
-    vsd = ov.init_state_dict(meta["vae_cfg"], seed=meta["vae_seed"])
-    usd = ou.init_state_dict(meta["upsampler_cfg"], seed=meta["upsampler_seed"])
-
-    def fingerprint(d):
-        return float(sum(v.double().abs().sum() for v in d.values()))
-
-    assert abs(fingerprint(vsd) - meta["vae_fingerprint"]) < 1e-6 * meta["vae_fingerprint"], "seeded VAE weights drifted"
-    assert abs(fingerprint(usd) - meta["upsampler_fingerprint"]) < 1e-6 * meta["upsampler_fingerprint"]
-    tok, enc = FakeTokenizer(), FakeTextEncoder(meta["dit_cfg"]["caption_channels"], seed=meta["text_encoder_seed"]).eval()
-    return t, meta, sd, vsd, usd, tok, enc
 
 
 def test_g15_multiscale_call_with_ltxv_kwargs(golden):
