@@ -21,7 +21,9 @@
  *     set (`ltxmi_gemm_args a = {0};` / memset): versions append optional fields at the tail
  *     (0.2: rowsumsq*, a_kblock* of ltxmi_gemm_args; q_rowsumsq*, q_norm*, rope_*, o_segment*
  *     of ltxmi_attn_args; 0.3: q_rstd*; 0.4: conv3d post_*; 0.5: redo_counter, force_exact of ltxmi_attn_args, y_norm, workspace of ltxmi_conv3d_args;
- *     0.6: lse* of ltxmi_attn_args), and a zero there means "off".  A caller must be
+ *     0.6: lse* of ltxmi_attn_args; 0.7: no field -- ltxmi_gemm_kernel_id, ltxmi_gemm_args.algo = 256 is honoured for every
+ *     shape, and the GEMM entry check refuses a bad epilogue and a residual / gate pointer off an 8-byte boundary),
+ *     and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
  *     switches its companion size / stride fields off whatever they hold.
  */
@@ -58,7 +60,14 @@ const char* ltxmi_arch(void);
  *   patchify_proj / proj_out       ltx_video/models/transformers/transformer3d.py:418,503
  *   adaln_single / caption_projection linears   transformer3d.py:428-433,448
  * W is the nn.Linear weight as stored in the checkpoint ([out,in], K contiguous).
- * Requirements: K % 64 == 0, N % 8 == 0, all pointers 16-byte aligned, lda/ldw/ldc % 8 == 0.
+ * Requirements (else LTXMI_ERR_UNSUPPORTED): K % 64 == 0, N % 8 == 0; A and W 16-byte aligned with lda, ldw % 8 == 0;
+ * C and bias 8-byte aligned with ldc % 4 == 0 (every kernel stores C through that: the tile kernels 8 bytes per lane, the
+ * persistent kernel 16 bytes per lane at 8-byte aligned addresses); lda >= K (or >= a_kblock), ldw >= K, ldc >= N; with
+ * GATE_RESIDUAL the residual, gate_table and gate_temb 8-byte aligned.  LTXMI_ERR_INVALID_ARG: a NULL A, W or C, a
+ * non-positive M, N or K, an epilogue outside ltxmi_epilogue (0.7: refused before anything is launched, so that
+ * ltxmi_gemm_kernel_id reports it), an algo outside {0, 128, 256}; GATE_RESIDUAL without a residual or with ldr < N or
+ * ldr % 4 != 0, a gate_table without gate_temb, with rows_per_group <= 0 or gate_ld % 4 != 0; a bad a_kblock or rowsumsq_cols.
+ * gate_temb must hold a row for every group, ceil(M / rows_per_group) of them: the index is not clamped.
  * ------------------------------------------------------------------------------- */
 typedef enum ltxmi_epilogue {
     LTXMI_EPI_NONE = 0,       /* C = acc + bias                                              */
@@ -96,6 +105,16 @@ typedef struct ltxmi_gemm_args {
 } ltxmi_gemm_args;
 
 int ltxmi_gemm_bf16(const ltxmi_gemm_args* args, void* stream);
+/* 0.7 -- which kernel ltxmi_gemm_bf16 runs for these arguments: 0 = the 128x128 tile kernel, 1 = the non-persistent 256x256
+ * tile kernel, 2 = the persistent 256x256 kernel; or the negative ltxmi_status ltxmi_gemm_bf16 would return for them
+ * (ltxmi_last_error() says why).  It is the launch's own decision code, host arithmetic only: nothing is launched, no device
+ * is needed and no pointer is dereferenced -- it reads M, N, K, the leading dimensions, algo, the fields the entry check
+ * validates, and the ADDRESSES of C, bias and the residual (alignment).  By shape (algo = 0): id 2 when M >= 768, N >= 256,
+ * ceil(M/256) * ceil(N/256) >= 128, K >= 128, M * ldc * 2 < 2^32, 256 * lda * 2 and 256 * ldw * 2 < 2^31, and the residual
+ * (if any) is 16-byte aligned with ldr % 8 == 0 and M * ldr * 2 < 2^32; id 1 when only the first three hold; else id 0.
+ * algo = 128 / 256 give id 0 / 1 for every accepted shape.  Every kernel accumulates over K in the same order: for the same
+ * arguments the three produce the same bits. */
+int ltxmi_gemm_kernel_id(const ltxmi_gemm_args* args);
 
 /* ---------------------------------------------------------------------------------
  * Fused standardisation + AdaLN modulation

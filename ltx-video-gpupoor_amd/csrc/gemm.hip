@@ -985,26 +985,82 @@ int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream
 
 using namespace ltxmi;
 
-extern "C" int ltxmi_gemm_bf16(const ltxmi_gemm_args* a, void* stream) {
-    LTXMI_REQUIRE(a && a->A && a->W && a->C, LTXMI_ERR_INVALID_ARG, "ltxmi_gemm_bf16: NULL argument");
+// Kernels behind ltxmi_gemm_bf16, as ltxmi_gemm_kernel_id reports them
+enum { GEMM_TILE128 = 0, GEMM_TILE256 = 1, GEMM_PERSISTENT256 = 2 };
+
+// The ONE place that validates a GEMM call and picks its kernel: ltxmi_gemm_bf16 launches what this returns and
+// ltxmi_gemm_kernel_id reports it.  Pure host arithmetic on the struct: no device call, no device memory read.
+// Returns GEMM_* or the negative ltxmi_status (error text set).
+static int gemm_plan(const ltxmi_gemm_args* a, const char* what) {
+    LTXMI_REQUIRE(a && a->A && a->W && a->C, LTXMI_ERR_INVALID_ARG, "%s: NULL argument", what);
     LTXMI_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, LTXMI_ERR_INVALID_ARG,
-                  "ltxmi_gemm_bf16: non-positive shape M=%d N=%d K=%d", a->M, a->N, a->K);
-    LTXMI_REQUIRE(a->K % 64 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: K=%d must be a multiple of 64", a->K);
-    LTXMI_REQUIRE(a->N % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: N=%d must be a multiple of 8", a->N);
+                  "%s: non-positive shape M=%d N=%d K=%d", what, a->M, a->N, a->K);
+    LTXMI_REQUIRE(a->K % 64 == 0, LTXMI_ERR_UNSUPPORTED, "%s: K=%d must be a multiple of 64", what, a->K);
+    LTXMI_REQUIRE(a->N % 8 == 0, LTXMI_ERR_UNSUPPORTED, "%s: N=%d must be a multiple of 8", what, a->N);
     LTXMI_REQUIRE(a->lda % 8 == 0 && a->ldw % 8 == 0 && a->ldc % 4 == 0 && (a->lda >= a->K || a->a_kblock > 0) && a->ldw >= a->K &&
                       a->ldc >= a->N,
-                  LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: bad leading dimensions lda=%lld ldw=%lld ldc=%lld",
+                  LTXMI_ERR_UNSUPPORTED, "%s: bad leading dimensions lda=%lld ldw=%lld ldc=%lld", what,
                   (long long)a->lda, (long long)a->ldw, (long long)a->ldc);
     LTXMI_REQUIRE((((uintptr_t)a->A | (uintptr_t)a->W) & 15) == 0 && (((uintptr_t)a->C) & 7) == 0 &&
                       (((uintptr_t)a->bias) & 7) == 0,
-                  LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: pointers must be 16-byte (A, W) / 8-byte (C, bias) aligned");
+                  LTXMI_ERR_UNSUPPORTED, "%s: pointers must be 16-byte (A, W) / 8-byte (C, bias) aligned", what);
+    LTXMI_REQUIRE(a->epilogue >= LTXMI_EPI_NONE && a->epilogue <= LTXMI_EPI_GATE_RESIDUAL, LTXMI_ERR_INVALID_ARG,
+                  "%s: bad epilogue %d", what, a->epilogue);
     if (a->epilogue == LTXMI_EPI_GATE_RESIDUAL) {
         LTXMI_REQUIRE(a->residual && a->ldr >= a->N && a->ldr % 4 == 0, LTXMI_ERR_INVALID_ARG,
-                      "ltxmi_gemm_bf16: GATE_RESIDUAL needs a residual with ldr >= N");
+                      "%s: GATE_RESIDUAL needs a residual with ldr >= N", what);
         if (a->gate_table)
             LTXMI_REQUIRE(a->gate_temb && a->rows_per_group > 0 && a->gate_ld % 4 == 0, LTXMI_ERR_INVALID_ARG,
-                          "ltxmi_gemm_bf16: gate_table given without gate_temb / rows_per_group");
+                          "%s: gate_table given without gate_temb / rows_per_group", what);
+        // (every kernel's epilogue reads these 8 bytes per lane; gate_temb is not looked at without a gate_table)
+        LTXMI_REQUIRE((((uintptr_t)a->residual | (uintptr_t)a->gate_table |
+                        (a->gate_table ? (uintptr_t)a->gate_temb : (uintptr_t)0)) & 7) == 0,
+                      LTXMI_ERR_UNSUPPORTED, "%s: residual, gate_table and gate_temb must be 8-byte aligned", what);
     }
+    if (a->a_kblock) {
+        LTXMI_REQUIRE(a->a_kblock > 0 && a->a_kblock % 64 == 0 && a->K % a->a_kblock == 0 && a->a_kblock_stride % 8 == 0 &&
+                          a->lda >= a->a_kblock,
+                      LTXMI_ERR_INVALID_ARG, "%s: a_kblock=%d must be a multiple of 64 that divides K, lda >= a_kblock", what,
+                      a->a_kblock);
+        LTXMI_REQUIRE(((int64_t)(a->K / a->a_kblock - 1) * a->a_kblock_stride + (int64_t)256 * a->lda) * 2 < (1ll << 31),
+                      LTXMI_ERR_UNSUPPORTED, "%s: K-blocked A spans more than 2 GiB per tile", what);
+    }
+    if (a->rowsumsq) {
+        LTXMI_REQUIRE(a->epilogue == LTXMI_EPI_NONE, LTXMI_ERR_UNSUPPORTED, "%s: rowsumsq needs the plain epilogue", what);
+        LTXMI_REQUIRE(a->rowsumsq_cols > 0 && a->rowsumsq_cols % 64 == 0 && a->rowsumsq_cols <= a->N &&
+                          a->rowsumsq_ld >= a->rowsumsq_cols / 64 && (((uintptr_t)a->rowsumsq) & 3) == 0,
+                      LTXMI_ERR_INVALID_ARG, "%s: rowsumsq_cols=%d must be a multiple of 64 within N, ld >= cols/64", what,
+                      a->rowsumsq_cols);
+        LTXMI_REQUIRE((int64_t)a->M * a->rowsumsq_ld * 4 < (1ll << 32), LTXMI_ERR_UNSUPPORTED, "%s: rowsumsq too large", what);
+    }
+    // a->algo (diagnostics): 0 = by shape, 128 = the 128x128 tile kernel, 256 = the non-persistent 256x256 one.  Both tile
+    // kernels take every shape accepted above (rows and columns past M / N are clamped on the reads, masked on the stores).
+    const int force_tile = a->algo;
+    LTXMI_REQUIRE(force_tile == 0 || force_tile == 128 || force_tile == 256, LTXMI_ERR_INVALID_ARG,
+                  "%s: algo %d not in {0, 128, 256}", what, force_tile);
+    if (force_tile == 128) return GEMM_TILE128;
+    if (force_tile == 256) return GEMM_TILE256;
+    // Tile choice: 256x256 (8 waves) when it still fills the 256 CUs, else 128x128 (4 waves,
+    // 2 blocks/CU); skinny problems (adaLN tables, text K/V) take the 128x128 path too.
+    const long t256 = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
+    constexpr long persist_min = 128;      // measured: 128 > 256 > 384 tiles for M = 4992 .. 9984
+    // (M >= 768: the stacked text K/V projection of a forward -- 3 x 256 text rows against every layer's [to_k; to_v])
+    if (a->M >= 768 && a->N >= 256 && t256 >= persist_min) {
+        const bool fits32 = ((int64_t)a->M * a->ldc * 2 < (1ll << 32)) && ((int64_t)256 * a->lda * 2 < (1ll << 31)) &&
+                            ((int64_t)256 * a->ldw * 2 < (1ll << 31));
+        // (the persistent kernel reads the residual through a buffer descriptor, in 16-byte pieces)
+        const bool res16 = !a->residual || (a->ldr % 8 == 0 && (((uintptr_t)a->residual) & 15) == 0 &&
+                                            (int64_t)a->M * a->ldr * 2 < (1ll << 32));
+        return a->K >= 128 && fits32 && res16 ? GEMM_PERSISTENT256 : GEMM_TILE256;
+    }
+    return GEMM_TILE128;
+}
+
+extern "C" int ltxmi_gemm_kernel_id(const ltxmi_gemm_args* a) { return gemm_plan(a, "ltxmi_gemm_kernel_id"); }
+
+extern "C" int ltxmi_gemm_bf16(const ltxmi_gemm_args* a, void* stream) {
+    const int kernel = gemm_plan(a, "ltxmi_gemm_bf16");
+    if (kernel < 0) return kernel;
     GemmParams p;
     p.A = (const uint16_t*)a->A; p.lda = a->lda;
     p.W = (const uint16_t*)a->W; p.ldw = a->ldw;
@@ -1026,46 +1082,14 @@ extern "C" int ltxmi_gemm_bf16(const ltxmi_gemm_args* a, void* stream) {
     p.sumsq_cols = a->rowsumsq ? a->rowsumsq_cols : 0;
     p.sumsq_ld = a->rowsumsq ? a->rowsumsq_ld : 0;
     p.a_kblk = a->a_kblock; p.a_kblk_stride = a->a_kblock_stride;
-    if (a->a_kblock) {
-        LTXMI_REQUIRE(a->a_kblock > 0 && a->a_kblock % 64 == 0 && a->K % a->a_kblock == 0 && a->a_kblock_stride % 8 == 0 &&
-                          a->lda >= a->a_kblock,
-                      LTXMI_ERR_INVALID_ARG, "ltxmi_gemm_bf16: a_kblock=%d must be a multiple of 64 that divides K, lda >= a_kblock",
-                      a->a_kblock);
-        LTXMI_REQUIRE(((int64_t)(a->K / a->a_kblock - 1) * a->a_kblock_stride + (int64_t)256 * a->lda) * 2 < (1ll << 31),
-                      LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: K-blocked A spans more than 2 GiB per tile");
-    }
-    if (a->rowsumsq) {
-        LTXMI_REQUIRE(a->epilogue == LTXMI_EPI_NONE, LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: rowsumsq needs the plain epilogue");
-        LTXMI_REQUIRE(a->rowsumsq_cols > 0 && a->rowsumsq_cols % 64 == 0 && a->rowsumsq_cols <= a->N &&
-                          a->rowsumsq_ld >= a->rowsumsq_cols / 64 && (((uintptr_t)a->rowsumsq) & 3) == 0,
-                      LTXMI_ERR_INVALID_ARG, "ltxmi_gemm_bf16: rowsumsq_cols=%d must be a multiple of 64 within N, ld >= cols/64",
-                      a->rowsumsq_cols);
-        LTXMI_REQUIRE((int64_t)a->M * a->rowsumsq_ld * 4 < (1ll << 32), LTXMI_ERR_UNSUPPORTED, "ltxmi_gemm_bf16: rowsumsq too large");
-    }
     hipStream_t s = (hipStream_t)stream;
     const int epi = a->rowsumsq ? EPI_SUMSQ
                                 : ((a->epilogue == LTXMI_EPI_GATE_RESIDUAL && !a->gate_table) ? EPI_RESIDUAL : a->epilogue);
-    // Tile choice: 256x256 (8 waves) when it still fills the 256 CUs, else 128x128 (4 waves,
-    // 2 blocks/CU); skinny problems (adaLN tables, text K/V) take the 128x128 path too.
-    const long t256 = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
-    // a->algo (diagnostics): 0 = by shape, 128 = the 128x128 tile kernel, 256 = the non-persistent 256x256 one
-    const int force_tile = a->algo;
-    LTXMI_REQUIRE(force_tile == 0 || force_tile == 128 || force_tile == 256, LTXMI_ERR_INVALID_ARG,
-                  "ltxmi_gemm_bf16: algo %d not in {0, 128, 256}", force_tile);
-    if (force_tile == 128) return launch_tile<128, 128, 2, 2, 0>(p, epi, s, "ltxmi_gemm_bf16");
-    constexpr long persist_min = 128;      // measured: 128 > 256 > 384 tiles for M = 4992 .. 9984
-    // (M >= 768: the stacked text K/V projection of a forward -- 3 x 256 text rows against every layer's [to_k; to_v])
-    if (a->M >= 768 && a->N >= 256 && t256 >= persist_min) {
-        const bool fits32 = ((int64_t)a->M * a->ldc * 2 < (1ll << 32)) && ((int64_t)256 * a->lda * 2 < (1ll << 31)) &&
-                            ((int64_t)256 * a->ldw * 2 < (1ll << 31));
-        // (the persistent kernel reads the residual through a buffer descriptor, in 16-byte pieces)
-        const bool res16 = !a->residual || (a->ldr % 8 == 0 && (((uintptr_t)a->residual) & 15) == 0 &&
-                                            (int64_t)a->M * a->ldr * 2 < (1ll << 32));
-        if (a->K >= 128 && fits32 && res16 && force_tile != 256)
-            return launch_persistent<256, 256, 2, 4>(p, epi, s, "ltxmi_gemm_bf16");
-        return launch_tile<256, 256, 2, 4, 0>(p, epi, s, "ltxmi_gemm_bf16");
+    switch (kernel) {
+        case GEMM_PERSISTENT256: return launch_persistent<256, 256, 2, 4>(p, epi, s, "ltxmi_gemm_bf16");
+        case GEMM_TILE256: return launch_tile<256, 256, 2, 4, 0>(p, epi, s, "ltxmi_gemm_bf16");
+        default: return launch_tile<128, 128, 2, 2, 0>(p, epi, s, "ltxmi_gemm_bf16");
     }
-    return launch_tile<128, 128, 2, 2, 0>(p, epi, s, "ltxmi_gemm_bf16");
 }
 
 #ifdef LTXMI_GEMM_STAMPS

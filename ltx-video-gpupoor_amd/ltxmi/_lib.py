@@ -76,6 +76,7 @@ SIGNATURES = {
     "ltxmi_last_error": (ctypes.c_char_p, []),
     "ltxmi_arch": (ctypes.c_char_p, []),
     "ltxmi_gemm_bf16": (c_int, [ctypes.POINTER(GemmArgs), c_void_p]),
+    "ltxmi_gemm_kernel_id": (c_int, [ctypes.POINTER(GemmArgs)]),
     "ltxmi_norm_modulate_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "ltxmi_rmsnorm_rope_bf16": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,

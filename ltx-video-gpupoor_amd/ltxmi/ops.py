@@ -103,11 +103,16 @@ def tensor_version(t):
         return -1
 
 
-def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
-         rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0):
-    """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  ``a``/``out``/``residual`` may be row-strided 2-D views.
-    gate_temb: 2-D view [groups, N] (row stride = gate_ld)."""
-    _chk_bf16(a, w, bias, out, residual, gate_table, gate_temb)
+def _chk_bf16_any_device(*ts):
+    for t in ts:
+        if t is not None and t.dtype != BF16:
+            raise TypeError(f"ltxmi: expected a bfloat16 tensor, got {t.dtype}")
+
+
+def _gemm_args(a, w, bias, out, epilogue, residual, gate_table, gate_temb, rows_per_group, algo, rowsumsq, rowsumsq_cols,
+               a_kblock, a_kblock_stride, allocate_out):
+    """The ltxmi_gemm_args of a ``gemm`` / ``gemm_kernel_id`` call -> (args, out, M, N, K).  ``out is None``: allocated
+    (allocate_out), or stood in for by what a fresh allocation always is -- contiguous and 16-byte aligned."""
     a2, M, lda = _rows(a)
     N, K = w.shape
     if a_kblock:
@@ -116,16 +121,19 @@ def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table
             raise ValueError(f"ltxmi.gemm: K-blocked a must be [M, {a_kblock}] with K={K} a multiple of the block")
     elif a2.shape[1] != K:
         raise ValueError(f"ltxmi.gemm: a is [{M},{a2.shape[1]}] but w is [{N},{K}]")
-    if out is None:
-        out = torch.empty((M, N), dtype=BF16, device=a.device)
-    o2, Mo, ldc = _rows(out)
-    if Mo != M or o2.shape[1] != N:
-        raise ValueError("ltxmi.gemm: bad out shape")
     args = _lib.GemmArgs()
+    if out is None and not allocate_out:
+        args.C, args.ldc = 256, N
+    else:
+        if out is None:
+            out = torch.empty((M, N), dtype=BF16, device=a.device)
+        o2, Mo, ldc = _rows(out)
+        if Mo != M or o2.shape[1] != N:
+            raise ValueError("ltxmi.gemm: bad out shape")
+        args.C, args.ldc = o2.data_ptr(), ldc
     args.A, args.lda = a2.data_ptr(), lda
     args.W, args.ldw = w.data_ptr(), w.stride(0)
     args.bias = bias.data_ptr() if bias is not None else None
-    args.C, args.ldc = o2.data_ptr(), ldc
     args.M, args.N, args.K = M, N, K
     args.epilogue = epilogue
     if residual is not None:
@@ -144,10 +152,35 @@ def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table
                 or rowsumsq.shape[1] * 64 < rowsumsq_cols:
             raise ValueError("ltxmi.gemm: rowsumsq must be fp32 [M, >= rowsumsq_cols/64]")
         args.rowsumsq, args.rowsumsq_cols, args.rowsumsq_ld = rowsumsq.data_ptr(), rowsumsq_cols, rowsumsq.stride(0)
+    return args, out, M, N, K
+
+
+def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
+         rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0):
+    """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  ``a``/``out``/``residual`` may be row-strided 2-D views.
+    gate_temb: 2-D view [groups, N] (row stride = gate_ld)."""
+    _chk_bf16(a, w, bias, out, residual, gate_table, gate_temb)
+    args, out, M, N, K = _gemm_args(a, w, bias, out, epilogue, residual, gate_table, gate_temb, rows_per_group, algo,
+                                    rowsumsq, rowsumsq_cols, a_kblock, a_kblock_stride, True)
     tok = _prof_begin(("gemm", M, N, K, epilogue))
     check(lib.ltxmi_gemm_bf16(ctypes.byref(args), _stream()), "ltxmi_gemm_bf16")
     _prof_end(tok)
     return out
+
+
+GEMM_TILE128, GEMM_TILE256, GEMM_PERSISTENT256 = 0, 1, 2      # include/ltxmi.h: ltxmi_gemm_kernel_id
+
+
+def gemm_kernel_id(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
+                   rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0):
+    """Which kernel ``gemm`` runs for the same arguments (0 the 128x128 tile kernel, 1 the non-persistent 256x256 one,
+    2 the persistent 256x256 one), or the negative status ``gemm`` would raise on.  Built from the same struct as the
+    launch and decided by the same code; nothing is launched or read, so the tensors may live on any device (only their
+    shapes, strides and addresses count)."""
+    _chk_bf16_any_device(a, w, bias, out, residual, gate_table, gate_temb)
+    args = _gemm_args(a, w, bias, out, epilogue, residual, gate_table, gate_temb, rows_per_group, algo,
+                      rowsumsq, rowsumsq_cols, a_kblock, a_kblock_stride, False)[0]
+    return int(lib.ltxmi_gemm_kernel_id(ctypes.byref(args)))
 
 
 def norm_modulate(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):

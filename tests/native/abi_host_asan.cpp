@@ -71,6 +71,27 @@ int main() {
     expect_fail(ltxmi_gemm_bf16(&g, nullptr), "gemm(K-blocked A, no device)");
     g.a_kblock = 1000;
     expect_fail(ltxmi_gemm_bf16(&g, nullptr), "gemm(a_kblock not dividing K)");
+    // ltxmi_gemm_kernel_id: the launch's own decision, answered without a device
+    memset(&g, 0, sizeof g);
+    if (ltxmi_gemm_kernel_id(nullptr) != LTXMI_ERR_INVALID_ARG || ltxmi_gemm_kernel_id(&g) != LTXMI_ERR_INVALID_ARG) {
+        fprintf(stderr, "ltxmi_gemm_kernel_id(NULL / zeroed)\n");
+        ++g_bad;
+    }
+    g.A = p; g.W = p; g.C = p; g.lda = 2048; g.ldw = 2048; g.ldc = 6144; g.M = 4992; g.N = 6144; g.K = 2048;
+    for (int algo : {0, 128, 256, 7}) {
+        g.algo = algo;
+        const int want = algo == 0 ? 2 : (algo == 128 ? 0 : (algo == 256 ? 1 : LTXMI_ERR_INVALID_ARG));
+        if (ltxmi_gemm_kernel_id(&g) != want) {
+            fprintf(stderr, "ltxmi_gemm_kernel_id(algo %d) = %d, want %d\n", algo, ltxmi_gemm_kernel_id(&g), want);
+            ++g_bad;
+        }
+    }
+    g.algo = 0; g.M = 767;
+    if (ltxmi_gemm_kernel_id(&g) != 0) { fprintf(stderr, "ltxmi_gemm_kernel_id(M 767)\n"); ++g_bad; }
+    g.M = 4992; g.K = 64;
+    if (ltxmi_gemm_kernel_id(&g) != 1) { fprintf(stderr, "ltxmi_gemm_kernel_id(K 64)\n"); ++g_bad; }
+    g.K = 100;
+    if (ltxmi_gemm_kernel_id(&g) != LTXMI_ERR_UNSUPPORTED) { fprintf(stderr, "ltxmi_gemm_kernel_id(K 100)\n"); ++g_bad; }
     for (int M : {1, 63, 128, 9984, 32760}) {                  // every kernel-choice branch
         memset(&g, 0, sizeof g);
         g.A = p; g.W = p; g.C = p; g.lda = 512; g.ldw = 512; g.ldc = 512; g.M = M; g.N = 512; g.K = 512;

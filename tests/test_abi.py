@@ -141,6 +141,145 @@ def test_attention_kernel_id_table(case):
     assert _lib.lib.ltxmi_attention_kernel_id(*shape) == want
 
 
+# ltxmi_gemm_kernel_id over the product's shapes and one row on each side of every threshold of the selection.  Each row is
+# (what, M, N, K, overrides of the struct built by _gemm_geometry, id).  Ids: 0 the 128x128 tile kernel, 1 the non-persistent
+# 256x256 one, 2 the persistent 256x256 one; negative = the ltxmi_status the launch would return.  The ids are worked out
+# by hand from include/ltxmi.h (tiles = ceil(M/256) * ceil(N/256)), not read off the library.
+GEMM_KERNEL_IDS = [
+    # M >= 768 (3 x 43 = 129 tiles either side)
+    ("M767", 767, 11008, 128, {}, 0),
+    ("M768", 768, 11008, 128, {}, 2),
+    # N >= 256 (128 tiles either side)
+    ("N248", 32768, 248, 128, {}, 0),
+    ("N256", 32768, 256, 128, {}, 2),
+    # >= 128 tiles: 8 x 15 = 120, 8 x 16 = 128 (the last N tile 8 columns wide), 8 x 16 exactly; 127 x 1 and 128 x 1
+    ("tiles120", 2048, 3840, 128, {}, 0),
+    ("tiles128_ragged", 2048, 3848, 128, {}, 2),
+    ("tiles128", 2048, 4096, 128, {}, 2),
+    ("tiles127", 32512, 256, 128, {}, 0),
+    ("tiles128_tall", 32513, 256, 128, {}, 2),
+    # K >= 128 at a persistent-sized shape
+    ("K64", 4097, 2056, 64, {}, 1),
+    ("K128", 4097, 2056, 128, {}, 2),
+    # the residual the persistent kernel reads 16 bytes at a time
+    ("ldr_mod8_0", 4097, 2056, 128, dict(epilogue=3, residual=0, ldr=2064), 2),
+    ("ldr_mod8_4", 4097, 2056, 128, dict(epilogue=3, residual=0, ldr=2060), 1),
+    ("res_plus8", 4097, 2056, 128, dict(epilogue=3, residual=8, ldr=2064), 1),
+    ("res_plus16", 4097, 2056, 128, dict(epilogue=3, residual=16, ldr=2064), 2),
+    ("res_span_2p32", 1048576, 256, 128, dict(epilogue=3, residual=0, ldr=2048, ldc=256), 1),
+    ("res_span_under", 1048576, 256, 128, dict(epilogue=3, residual=0, ldr=2040, ldc=256), 2),
+    # 32-bit byte offsets: M * ldc * 2 < 2^32, 256 * lda * 2 < 2^31, 256 * ldw * 2 < 2^31
+    ("c_span_under", 1048576, 256, 128, dict(ldc=2044), 2),
+    ("c_span_2p32", 1048576, 256, 128, dict(ldc=2048), 1),
+    ("lda_under", 2048, 4096, 128, dict(lda=(1 << 22) - 8), 2),
+    ("lda_2p31", 2048, 4096, 128, dict(lda=1 << 22), 1),
+    ("ldw_under", 2048, 4096, 128, dict(ldw=(1 << 22) - 8), 2),
+    ("ldw_2p31", 2048, 4096, 128, dict(ldw=1 << 22), 1),
+    # C only 8-byte aligned with ldc % 8 == 4: accepted, and no reason to leave the persistent kernel
+    ("c_plus8_ldc4", 4097, 2056, 128, dict(C=8, ldc=2060), 2),
+    ("c_plus8_ldc4_small", 129, 136, 64, dict(C=8, ldc=140), 0),
+    # algo (diagnostics): 128 / 256 hold for every accepted shape
+    ("small", 16, 16, 64, {}, 0),
+    ("small_algo128", 16, 16, 64, dict(algo=128), 0),
+    ("small_algo256", 16, 16, 64, dict(algo=256), 1),
+    ("one_row_algo256", 1, 8, 64, dict(algo=256), 1),
+    ("mid_algo256", 2048, 2048, 2048, dict(algo=256), 1),
+    ("mid_algo0", 2048, 2048, 2048, {}, 0),
+    ("large_algo128", 2048, 4096, 128, dict(algo=128), 0),
+    ("large_algo256", 2048, 4096, 128, dict(algo=256), 1),
+    ("algo7", 2048, 4096, 128, dict(algo=7), -1),
+    # refused arguments
+    ("K100", 16, 16, 100, dict(lda=128, ldw=128), -2),
+    ("N12", 16, 12, 64, {}, -2),
+    ("M0", 0, 16, 64, {}, -1),
+    ("ldc_mod4", 16, 16, 64, dict(ldc=18), -2),
+    ("ldc_below_N", 16, 16, 64, dict(ldc=8), -2),
+    ("lda_mod8", 16, 16, 64, dict(lda=68), -2),
+    ("c_plus4", 16, 16, 64, dict(C=4), -2),
+    ("a_plus8", 16, 16, 64, dict(A=8), -2),
+    ("bias_plus4", 16, 16, 64, dict(bias=4), -2),
+    ("epilogue99", 16, 16, 64, dict(epilogue=99), -1),
+    ("gate_without_residual", 16, 16, 64, dict(epilogue=3), -1),
+    ("gate_table_without_temb", 16, 16, 64, dict(epilogue=3, residual=0, ldr=16, gate_table=0), -1),
+    ("ldr_mod4", 16, 16, 64, dict(epilogue=3, residual=0, ldr=18), -1),
+    ("ldr_below_N", 16, 16, 64, dict(epilogue=3, residual=0, ldr=8), -1),
+    ("gate_ld_mod4", 16, 16, 64, dict(epilogue=3, residual=0, ldr=16, gate_table=0, gate_temb=0, gate_ld=18), -1),
+    # the epilogue reads the residual and the gate rows 8 bytes per lane
+    ("res_plus4", 16, 16, 64, dict(epilogue=3, residual=4, ldr=16), -2),
+    ("res_plus8_small", 16, 16, 64, dict(epilogue=3, residual=8, ldr=16), 0),
+    ("gate_table_plus4", 16, 16, 64, dict(epilogue=3, residual=0, ldr=16, gate_table=4, gate_temb=0, gate_ld=16), -2),
+    ("gate_temb_plus4", 16, 16, 64, dict(epilogue=3, residual=0, ldr=16, gate_table=0, gate_temb=4, gate_ld=16), -2),
+    ("gate_temb_plus8", 16, 16, 64, dict(epilogue=3, residual=0, ldr=16, gate_table=8, gate_temb=8, gate_ld=16), 0),
+    ("rowsumsq_with_gelu", 2048, 4096, 128, dict(epilogue=1, rowsumsq=0, rowsumsq_cols=64, rowsumsq_ld=1), -2),
+    ("rowsumsq_cols_mod64", 2048, 4096, 128, dict(rowsumsq=0, rowsumsq_cols=96, rowsumsq_ld=2), -1),
+    ("rowsumsq_192", 2048, 4096, 128, dict(rowsumsq=0, rowsumsq_cols=192, rowsumsq_ld=6), 2),
+    ("a_kblock_not_dividing", 2048, 4096, 256, dict(a_kblock=192, a_kblock_stride=2048 * 192, lda=192), -1),
+    # the product's own launches (14976 = 3 x 4992 tokens): QKV, FF1, FF2, to_out on the K-blocked receive buffer of the
+    # Ulysses return exchange (2 and 8 ranks), and the stacked text K/V projection (3 x 256 text rows, 28 layers' [to_k; to_v])
+    ("qkv", 14976, 6144, 2048, {}, 2),
+    ("ff1", 14976, 8192, 2048, dict(epilogue=1), 2),
+    ("ff2", 14976, 2048, 8192, dict(epilogue=3, residual=0, ldr=2048, gate_table=0, gate_temb=0, gate_ld=12288,
+                                    rows_per_group=4992), 2),
+    ("to_out_kblocked_2", 14976, 2048, 2048, dict(epilogue=3, residual=0, ldr=2048, gate_table=0, gate_temb=0, gate_ld=12288,
+                                                  rows_per_group=4992, lda=1024, a_kblock=1024,
+                                                  a_kblock_stride=14976 * 1024), 2),
+    ("to_out_kblocked_8", 1872, 2048, 2048, dict(epilogue=3, residual=0, ldr=2048, lda=256, a_kblock=256,
+                                                 a_kblock_stride=1872 * 256), 0),
+    ("text_kv_stacked", 768, 114688, 2048, {}, 2),
+    ("text_kv_one_prompt", 256, 114688, 2048, {}, 0),
+    ("adaln_table", 3, 12288, 2048, {}, 0),
+]
+
+
+def _gemm_geometry(M, N, K, over):
+    """A ltxmi_gemm_args of that geometry on fake addresses (nothing is dereferenced): pointer-valued overrides are byte
+    offsets from a 64-byte aligned base."""
+    from ltxmi import _lib
+    a = _lib.GemmArgs()
+    base = 1 << 30
+    a.A = a.W = a.C = base
+    a.M, a.N, a.K = M, N, K
+    a.lda = a.ldw = K
+    a.ldc = N
+    a.rows_per_group = 1
+    for k, v in over.items():
+        setattr(a, k, base + v if k in ("A", "W", "C", "bias", "residual", "gate_table", "gate_temb", "rowsumsq") else v)
+    return a
+
+
+@pytest.mark.parametrize("case", GEMM_KERNEL_IDS, ids=lambda c: c[0])
+def test_gemm_kernel_id_table(case):
+    from ltxmi import _lib
+    what, M, N, K, over, want = case
+    a = _gemm_geometry(M, N, K, over)
+    got = _lib.lib.ltxmi_gemm_kernel_id(ctypes.byref(a))
+    assert got == want, (what, got, _lib.lib.ltxmi_last_error())
+    if want < 0:
+        assert _lib.lib.ltxmi_last_error()
+        # the launch refuses the same arguments with the same status, before it needs a device
+        assert _lib.lib.ltxmi_gemm_bf16(ctypes.byref(a), None) == want
+
+
+def test_gemm_kernel_id_through_ops_needs_no_device():
+    """ops.gemm_kernel_id builds the struct ops.gemm builds: host tensors give the geometry (never touched)."""
+    import torch
+    from ltxmi import ops
+    a, w = torch.empty(5000, 192, dtype=torch.bfloat16), torch.empty(4104, 192, dtype=torch.bfloat16)
+    assert ops.gemm_kernel_id(a, w) == ops.GEMM_PERSISTENT256 == 2
+    assert ops.gemm_kernel_id(a, w, algo=256) == ops.GEMM_TILE256 == 1
+    assert ops.gemm_kernel_id(a, w, algo=128) == ops.GEMM_TILE128 == 0
+    assert ops.gemm_kernel_id(a[:767], w) == 0
+    res = torch.empty(5000, 4108, dtype=torch.bfloat16)
+    assert ops.gemm_kernel_id(a, w, epilogue=ops.EPI_GATE_RESIDUAL, residual=res[:, :4104]) == 1
+    out = torch.empty(5000, 4112, dtype=torch.bfloat16)
+    assert ops.gemm_kernel_id(a, w, out=out[:, :4104], epilogue=ops.EPI_GATE_RESIDUAL, residual=out[:, :4104]) == 2
+    blocked = torch.empty(3, 5000, 64, dtype=torch.bfloat16)
+    assert ops.gemm_kernel_id(blocked[0], w, a_kblock=64, a_kblock_stride=5000 * 64) == 2
+    assert ops.gemm_kernel_id(a, w, algo=7) == -1
+    with pytest.raises(TypeError):
+        ops.gemm_kernel_id(a.float(), w)
+
+
 def test_host_ops_refuse_cpu_tensors():
     """The product path has no CPU fallback: CPU tensors are an error, not a slow path."""
     import torch

@@ -39,11 +39,12 @@ def rnd(*shape, seed=0, scale=1.0):
 
 # ------------------------------------------------------------------------------- GEMM
 @pytest.mark.parametrize("M,N,K", [(300, 256, 128), (1000, 136, 256), (128, 128, 64), (3, 768, 256),
-                                   (6144, 4096, 256),        # takes the 256x256 / 8-wave tile
-                                   (6145, 4104, 128)])       # 256x256 tile with ragged M and N
+                                   (6144, 4096, 256),        # the persistent 256x256 kernel (24 x 16 tiles)
+                                   (6145, 4104, 128)])       # ... with ragged M and N (25 x 17 tiles)
 def test_gemm_bias(M, N, K):
     from ltxmi import ops
     a, w, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5), rnd(N, seed=3)
+    assert ops.gemm_kernel_id(a.to(DEV), w.to(DEV), b.to(DEV)) == (2 if M >= 6144 else 0)
     out = ops.gemm(a.to(DEV), w.to(DEV), b.to(DEV))
     truth = a.float() @ w.float().T + b.float()
     check(out, truth, what=f"gemm {M}x{N}x{K}")
@@ -753,22 +754,26 @@ def test_adain_filter(dtype):
 
 # ------------------------------------------------------------------ randomised shape sweeps
 def test_gemm_kernels_agree_bit_for_bit():
-    """The dispatcher picks a kernel from M (128x128 tiles / 256x256 tiles / persistent).  All of them accumulate over K in
+    """The dispatcher picks a kernel by shape (128x128 tiles / persistent 256x256; algo 128 / 256 force the 128x128 and the
+    non-persistent 256x256 tile kernels: the ids are asserted).  All of them accumulate over K in
     the same order with the same MFMA shape and share the epilogue arithmetic, so a row's result does not depend on the
     choice -- which is what makes running a sub-batch of rows bit-identical to running them all (stg_alias_blocks)."""
     from ltxmi import ops
-    for case, (M, N, K) in enumerate([(2048, 2048, 2048), (1500, 6144, 1024), (4992, 8192, 2048), (3000, 2048, 4096)]):
+    # (id by shape: 64 / 144 / 640 / 96 tiles of 256x256 against the persistent kernel's floor of 128)
+    for case, (M, N, K, by_shape) in enumerate([(2048, 2048, 2048, 0), (1500, 6144, 1024, 2), (4992, 8192, 2048, 2), (3000, 2048, 4096, 0)]):
         a, w, b = rnd(M, K, seed=40 + case).to(DEV), rnd(N, K, seed=50 + case, scale=K ** -0.5).to(DEV), rnd(N, seed=60 + case).to(DEV)
         res = rnd(M, N, seed=70 + case).to(DEV)
         gt, ge = rnd(N, seed=80 + case).to(DEV), rnd(3, N, seed=90 + case).to(DEV)
         for epi in (ops.EPI_NONE, ops.EPI_GELU_TANH, ops.EPI_SILU, ops.EPI_GATE_RESIDUAL):
             kw = dict(residual=res, gate_table=gt, gate_temb=ge, rows_per_group=(M + 2) // 3) if epi == ops.EPI_GATE_RESIDUAL else {}
+            assert [ops.gemm_kernel_id(a, w, b, epilogue=epi, algo=al, **kw) for al in (0, 128, 256)] == [by_shape, 0, 1]
             outs = [ops.gemm(a, w, b, epilogue=epi, algo=al, **kw) for al in (0, 128, 256)]
             assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), f"gemm {M}x{N}x{K} epi {epi}: kernels differ"
         # the row sums of squares the QKV projection hands to the attention kernel (q's RMSNorm factor)
         sums = []
         for al in (0, 128, 256):
             ss = torch.zeros(M, N // 64, device=DEV)
+            assert ops.gemm_kernel_id(a, w, b, algo=al, rowsumsq=ss, rowsumsq_cols=N) == {0: by_shape, 128: 0, 256: 1}[al]
             o = ops.gemm(a, w, b, algo=al, rowsumsq=ss, rowsumsq_cols=N)
             sums.append(ss)
         assert torch.equal(sums[0], sums[1]) and torch.equal(sums[0], sums[2]), f"gemm {M}x{N}x{K}: row sums of squares differ between kernels"
@@ -779,19 +784,24 @@ def test_gemm_kernels_agree_bit_for_bit():
 
 
 def test_gemm_random_shapes_persistent_path():
-    """Seeded random (M, N, K) on the persistent 256x256 kernel (M >= 1024, >= 384 tiles): ragged last
-    M/N tiles through the per-tile buffer descriptors, odd tile counts per workgroup, every epilogue, a
-    result that must stay in bounds (guard columns/rows around the output are checked untouched)."""
+    """Seeded random (M, N, K) on the persistent 256x256 kernel (whatever ops.gemm_kernel_id says is one; a third of the
+    cases below 384 tiles, where workgroups have one tile or a mix of one and two): ragged last M/N tiles through the
+    per-tile buffer descriptors, odd tile counts per workgroup, every epilogue, a result that must stay in bounds (guard
+    columns/rows around the output are checked untouched)."""
     import random
     from ltxmi import ops
     rng = random.Random(1234)
+    few = 0
     for case in range(14):
-        while True:
-            M = rng.randrange(1024, 9000)
-            N = 8 * rng.randrange(32, 800)
-            if ((M + 255) // 256) * ((N + 255) // 256) >= 384:
-                break
         K = 64 * rng.randrange(2, 17)
+        while True:
+            M = rng.randrange(768, 9000)
+            N = 8 * rng.randrange(32, 800)
+            if ops.gemm_kernel_id(torch.empty(M, K, dtype=BF), torch.empty(N, K, dtype=BF)) != 2:
+                continue
+            if (((M + 255) // 256) * ((N + 255) // 256) < 384) == (case % 3 == 0):
+                break
+        few += case % 3 == 0
         epi = [ops.EPI_NONE, ops.EPI_GELU_TANH, ops.EPI_SILU, ops.EPI_GATE_RESIDUAL][case % 4]
         a, w, b = rnd(M, K, seed=200 + case), rnd(N, K, seed=300 + case, scale=K ** -0.5), rnd(N, seed=400 + case)
         pre = a.float() @ w.float().T + b.float()
@@ -800,9 +810,11 @@ def test_gemm_random_shapes_persistent_path():
         if epi == ops.EPI_GATE_RESIDUAL:
             res = rnd(M, N, seed=500 + case)
             out.copy_(res.to(DEV))
+            assert ops.gemm_kernel_id(a.to(DEV), w.to(DEV), b.to(DEV), out=out, epilogue=epi, residual=out) == 2
             ops.gemm(a.to(DEV), w.to(DEV), b.to(DEV), out=out, epilogue=epi, residual=out)
             truth = res.float() + pre
         else:
+            assert ops.gemm_kernel_id(a.to(DEV), w.to(DEV), b.to(DEV), out=out, epilogue=epi) == 2
             ops.gemm(a.to(DEV), w.to(DEV), b.to(DEV), out=out, epilogue=epi)
             truth = {ops.EPI_NONE: pre, ops.EPI_GELU_TANH: torch.nn.functional.gelu(pre, approximate="tanh"),
                      ops.EPI_SILU: torch.nn.functional.silu(pre)}[epi]
@@ -810,6 +822,7 @@ def test_gemm_random_shapes_persistent_path():
         g = guard.clone()
         g[1:M + 1, 8:N + 8] = 7.0
         assert (g == 7.0).all(), f"random gemm {M}x{N}x{K}: wrote outside the output"
+    assert few == 5
 
 
 def test_attention_random_shapes():
@@ -1388,11 +1401,14 @@ def test_attention_reads_token_major_and_writes_segmented(B, H, N, P):
     assert torch.equal(got, want)
 
 
-@pytest.mark.parametrize("M,N,K,P,epi", [(1872, 2048, 2048, 8, "gate"), (5000, 384, 512, 2, "none"), (300, 256, 256, 4, "none")])
+@pytest.mark.parametrize("M,N,K,P,epi", [(1872, 2048, 2048, 8, "gate"), (5000, 384, 512, 2, "none"), (300, 256, 256, 4, "none"),
+                                         (5000, 2048, 2048, 8, "gate")])
 def test_gemm_k_blocked_operand(M, N, K, P, epi):
-    """A = the return all-to-all's receive buffer [P][M][K/P], consumed in place (K-blocked), incl. the persistent kernel
-    and the gate + residual epilogue of to_out."""
+    """A = the return all-to-all's receive buffer [P][M][K/P], consumed in place (K-blocked), with the gate + residual
+    epilogue of to_out.  The first three shapes have 64, 40 and 2 tiles of 256x256 and run the 128x128 kernel; the last
+    (20 x 8 tiles) runs the persistent kernel, as to_out does in the product."""
     from ltxmi import ops
+    want_id = 2 if M == 5000 and N == 2048 else 0
     g = torch.Generator(device=DEV).manual_seed(200)
     a = (torch.randn(M, K, generator=g, device=DEV) * 0.5).to(BF)
     w = (torch.randn(N, K, generator=g, device=DEV) * K ** -0.5).to(BF)
@@ -1401,12 +1417,18 @@ def test_gemm_k_blocked_operand(M, N, K, P, epi):
     kw = {}
     if epi == "gate":
         res = torch.randn(M, N, generator=g, device=DEV).to(BF)
+        # (three groups exactly: the kernels do not clamp the group index, so rows_per_group rounds UP -- 624 and 1667)
         kw = dict(epilogue=ops.EPI_GATE_RESIDUAL, gate_table=torch.randn(N, generator=g, device=DEV).to(BF),
-                  gate_temb=torch.randn(3, N, generator=g, device=DEV).to(BF), rows_per_group=M // 3)
+                  gate_temb=torch.randn(3, N, generator=g, device=DEV).to(BF), rows_per_group=(M + 2) // 3)
+        assert ops.gemm_kernel_id(a, w, b, residual=res, out=torch.empty_like(res), **kw) == want_id
+        assert ops.gemm_kernel_id(blocked[0], w, b, residual=res, out=torch.empty_like(res), a_kblock=K // P,
+                                  a_kblock_stride=M * (K // P), **kw) == want_id
         want = ops.gemm(a, w, b, residual=res.clone(), out=torch.empty_like(res), **kw)
         got = ops.gemm(blocked[0], w, b, residual=res.clone(), out=torch.empty_like(res), a_kblock=K // P,
                        a_kblock_stride=M * (K // P), **kw)
     else:
+        assert ops.gemm_kernel_id(a, w, b) == want_id
+        assert ops.gemm_kernel_id(blocked[0], w, b, a_kblock=K // P, a_kblock_stride=M * (K // P)) == want_id
         want = ops.gemm(a, w, b)
         got = ops.gemm(blocked[0], w, b, a_kblock=K // P, a_kblock_stride=M * (K // P))
     assert torch.equal(got, want)
@@ -1449,8 +1471,8 @@ def test_gemm_ignores_rowsumsq_fields_without_a_pointer():
     geometry from those fields."""
     import ctypes
     from ltxmi import _lib, ops
-    M, N, K = 2048, 512, 256                                 # persistent 256x256 kernel (M >= 1024, >= 128 tiles? no: small) ...
-    for (M, N, K) in ((2048, 512, 256), (8192, 4096, 128)):  # the 128x128 tile kernel and the persistent 256x256 one
+    # the 128x128 tile kernel (8 x 2 tiles of 256x256) and the persistent 256x256 one (32 x 16 tiles, floor 128)
+    for (M, N, K, kernel) in ((2048, 512, 256, 0), (8192, 4096, 128, 2)):
         a, w = rnd(M, K, seed=41).to(DEV), rnd(N, K, seed=42, scale=K ** -0.5).to(DEV)
         guard = torch.full((M * N + 4096,), 7.0, dtype=BF, device=DEV)
         out = guard[:M * N].view(M, N)
@@ -1459,6 +1481,7 @@ def test_gemm_ignores_rowsumsq_fields_without_a_pointer():
         args.C, args.ldc, args.M, args.N, args.K = out.data_ptr(), N, M, N, K
         args.rows_per_group = 1
         args.rowsumsq, args.rowsumsq_cols, args.rowsumsq_ld = None, 0x7fffff00, -12345
+        assert _lib.lib.ltxmi_gemm_kernel_id(ctypes.byref(args)) == kernel
         _lib.check(_lib.lib.ltxmi_gemm_bf16(ctypes.byref(args), ops._stream()), "ltxmi_gemm_bf16")
         torch.cuda.synchronize()
         check(out, a.float().cpu() @ w.float().cpu().T, what=f"gemm {M}x{N}x{K} with garbage rowsumsq fields")
