@@ -469,6 +469,14 @@ int ltxmi_image_cond_noise(void* latents, const void* init_latents, const void* 
  *                   is read twice and written once.  y may be x (in place).
  *   pixel_shuffle2d: x [frames, H, W, 4C] with channel (p1*2 + p2)*C + c -> y [frames, 2H, 2W, C]
  *                   (PixelShuffleND(2) :93-96 with the conv rows packed (p1 p2 c)).
+ *   pixel_shuffle_nd: PixelShuffleND(1 | 2 | 3) with the temporal modes' frame trim folded in (pixel_shuffle.py:12-33,
+ *                   latent_upsampler.py:83-97,136-138).  pt, ps in {1, 2} (not both 1): the upscale factor in time and
+ *                   in space (H and W share ps).  x [B, T, H, W, pt*ps*ps*C] with channel ((p1*ps + p2)*ps + p3)*C + c
+ *                   (the conv rows packed (p1 p2 p3 c)) -> y [B, pt*T - drop_first, ps*H, ps*W, C],
+ *                   y[b, t*pt + p1 - drop_first, h*ps + p2, w*ps + p3, c] = x[b, t, h, w, (p1, p2, p3, c)].
+ *                   drop_first in {0, 1} (1 needs pt = 2) is the reference's x[:, :, 1:]: the trim is in the store
+ *                   address, the slice t*pt + p1 < drop_first is neither read nor written.  C % 8 == 0; 16-byte
+ *                   copies, 64-bit offsets; x is read once (less the trimmed slice) and y written once.
  *   adain_filter:   per (b, c) plane: out = lerp(x, (x - mean_x)/std_x * std_ref + mean_ref, factor);
  *                   latents [planes, n], reference [planes, n_ref], fp32 (is_bf16 = 0) or bf16.
  * ------------------------------------------------------------------------------- */
@@ -477,6 +485,8 @@ int ltxmi_groupnorm_silu_bf16(const void* x, void* y, const void* residual, int3
                               float* workspace, void* stream);
 int ltxmi_pixel_shuffle2d_ndhwc_bf16(const void* x, void* y, int64_t frames, int32_t H, int32_t W, int32_t C,
                                      void* stream);
+int ltxmi_pixel_shuffle_nd_ndhwc_bf16(const void* x, void* y, int32_t B, int32_t T, int32_t H, int32_t W, int32_t C,
+                                      int32_t pt, int32_t ps, int32_t drop_first, void* stream);
 /* Tile cross-fade of the tiled VAE decode / encode (blend_z / blend_v / blend_h, vae.py:193-221), in place in b:
  *   b[o, z, i] = a[o, len_a - extent + z, i] * (1 - z / extent) + b[o, z, i] * (z / extent),   z < extent,
  * both tensors contiguous and viewed as [outer][len][inner] around the blended axis; dtype: 0 fp32, 1 bf16, 2 fp16 (the

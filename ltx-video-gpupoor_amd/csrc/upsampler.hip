@@ -1,7 +1,7 @@
 // upsampler.hip -- the HBM-bound pieces of the multi-scale bridge between pass 1 and pass 2
 // (LatentUpsampler, latent_upsampler.py:15-149; adain_filter_latent, pipeline_ltx_video.py:1709-1737):
-// GroupNorm(32) (+ residual) + SiLU over channels-last activations, the 2-D pixel shuffle after the
-// upsampling convolution, and the per-channel AdaIN statistics transfer.  The convolutions themselves
+// GroupNorm(32) (+ residual) + SiLU over channels-last activations, the pixel shuffle after the
+// upsampling convolution (2-D; N-D with the temporal modes' frame trim), and the per-channel AdaIN statistics transfer.  The convolutions themselves
 // are the implicit GEMM of gemm.hip (kernel_t / time_pad_zeros options).
 #include <math.h>
 
@@ -158,6 +158,31 @@ __global__ void pixel_shuffle2d_kernel(const uint16_t* __restrict__ x, uint16_t*
     }
 }
 
+// ---------------------------------------------------------------- N-D pixel shuffle + frame trim, channels-last
+// x [B, T, H, W, pt*ps*ps*C] with channel ((p1*ps + p2)*ps + p3)*C + c (conv rows packed that way) ->
+// y [B, pt*T - drop, ps*H, ps*W, C] = PixelShuffleND(1 | 2 | 3) (pixel_shuffle.py:12-33) followed by the temporal
+// modes' x[:, :, 1:] (latent_upsampler.py:136-138).  A thread owns one 16-byte chunk of y; the trim is the `+ drop` on
+// the output frame, so the source slice t*pt + p1 < drop is never touched.  lt / ls = log2(pt) / log2(ps) in {0, 1}.
+__global__ void pixel_shuffle_nd_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, int64_t T, int64_t H,
+                                        int64_t W, int C, int lt, int ls, int drop, int64_t total_chunks) {
+    const int64_t slots = C >> 3;
+    const int64_t To = (T << lt) - drop, Ho = H << ls, Wo = W << ls;
+    const int pmask_t = (1 << lt) - 1, pmask_s = (1 << ls) - 1;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total_chunks;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t slot = i % slots;
+        int64_t r = i / slots;
+        const int64_t xo = r % Wo; r /= Wo;
+        const int64_t yo = r % Ho; r /= Ho;
+        const int64_t to = r % To + drop;
+        const int64_t b = r / To;
+        const int64_t p = ((((to & pmask_t) << ls) + (yo & pmask_s)) << ls) + (xo & pmask_s);
+        const int64_t pos = ((b * T + (to >> lt)) * H + (yo >> ls)) * W + (xo >> ls);
+        const int64_t src = ((pos << (lt + 2 * ls)) + p) * C + slot * 8;
+        *(u32x4*)(y + i * 8) = *(const u32x4*)(x + src);
+    }
+}
+
 // ---------------------------------------------------------------- AdaIN (adain_filter_latent)
 template <typename T> __device__ __forceinline__ float ld(const T* p, int64_t i);
 template <> __device__ __forceinline__ float ld<float>(const float* p, int64_t i) { return p[i]; }
@@ -270,6 +295,24 @@ extern "C" int ltxmi_pixel_shuffle2d_ndhwc_bf16(const void* x, void* y, int64_t 
     hipLaunchKernelGGL(pixel_shuffle2d_kernel, dim3((unsigned)g), dim3(UP_THREADS), 0, (hipStream_t)stream,
                        (const uint16_t*)x, (uint16_t*)y, H, W, C, chunks);
     return check_launch("ltxmi_pixel_shuffle2d_ndhwc_bf16");
+}
+
+extern "C" int ltxmi_pixel_shuffle_nd_ndhwc_bf16(const void* x, void* y, int32_t B, int32_t T, int32_t H, int32_t W,
+                                                 int32_t C, int32_t pt, int32_t ps, int32_t drop_first, void* stream) {
+    LTXMI_REQUIRE(x && y, LTXMI_ERR_INVALID_ARG, "ltxmi_pixel_shuffle_nd_ndhwc_bf16: NULL argument");
+    LTXMI_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_pixel_shuffle_nd_ndhwc_bf16: bad sizes (C=%d must be a multiple of 8)", C);
+    LTXMI_REQUIRE((pt == 1 || pt == 2) && (ps == 1 || ps == 2) && pt * ps > 1, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_pixel_shuffle_nd_ndhwc_bf16: pt=%d, ps=%d must each be 1 or 2 and not both 1", pt, ps);
+    LTXMI_REQUIRE((drop_first == 0 || drop_first == 1) && drop_first < pt, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_pixel_shuffle_nd_ndhwc_bf16: drop_first=%d must be 0 or 1, and 1 only with pt = 2", drop_first);
+    const int64_t chunks = (int64_t)B * ((int64_t)pt * T - drop_first) * ps * H * ps * W * (C / 8);
+    int64_t g = (chunks + UP_THREADS - 1) / UP_THREADS;
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(pixel_shuffle_nd_kernel, dim3((unsigned)g), dim3(UP_THREADS), 0, (hipStream_t)stream,
+                       (const uint16_t*)x, (uint16_t*)y, (int64_t)T, (int64_t)H, (int64_t)W, C, pt - 1, ps - 1, drop_first,
+                       chunks);
+    return check_launch("ltxmi_pixel_shuffle_nd_ndhwc_bf16");
 }
 
 extern "C" int ltxmi_tile_blend(const void* a, void* b, int32_t dtype, int64_t outer, int64_t len_a, int64_t len_b,

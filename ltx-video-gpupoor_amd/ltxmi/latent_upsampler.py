@@ -9,9 +9,13 @@ Same config keys and parameter names (checkpoint-compatible with ltxv-spatial-up
 Activations are channels-last bf16.  nn.Conv3d(padding=1) / nn.Conv2d(padding=1) are the implicit GEMM of
 ``ltxmi_conv3d_ndhwc_bf16`` with zero padding in time (``time_pad_zeros``) or a per-frame 3x3 kernel
 (``kernel_t = 1``); GroupNorm(32) + SiLU (+ the ResBlock residual) is one statistics pass + one apply pass;
-the 2-D pixel shuffle is a 16-byte-vector copy because the upsampling conv's rows are packed (p1 p2 c);
-un_normalize / normalize ride on the NCDHW<->NDHWC layout kernels.  The temporal upsampler variants are
-not shipped by the reference (ltxv.py:194 loads the spatial one) and are rejected.
+the pixel shuffle is a 16-byte-vector copy because the upsampling conv's rows are packed (p1 .. pn c);
+un_normalize / normalize ride on the NCDHW<->NDHWC layout kernels.
+
+All three modes of the reference (:83-97, 136-142) run: spatial (Conv2d + PixelShuffleND(2), per frame), temporal
+(Conv3d + PixelShuffleND(1)) and spatial + temporal (Conv3d + PixelShuffleND(3)).  The two temporal modes drop
+the first output frame (``x[:, :, 1:]``); here that trim is the store address of the shuffle kernel
+(``ltxmi_pixel_shuffle_nd_ndhwc_bf16``), not a second pass.  They exist on the reference's dims == 3 branch only.
 """
 import json
 import math
@@ -36,18 +40,21 @@ class _ConvParams(nn.Module):
         self.bias = nn.Parameter((torch.rand(cout) * 2 - 1) * bound)
         self._packed = None
 
-    def packed(self, shuffle2d=False):
-        key = (self.weight.data_ptr(), shuffle2d)
+    def packed(self, shuffle=0):
+        """(weight [cout, taps * cin] tap-major, bias) in bf16.  shuffle = n in {1, 2, 3}: the rows feed PixelShuffleND(n),
+        whose channel split is (c p1 .. pn); they are reordered to (p1 .. pn c) so that the shuffle moves whole runs of c."""
+        key = (self.weight.data_ptr(), shuffle)
         if self._packed is None or self._packed[0] != key:
             with torch.no_grad():
                 cout = self.weight.shape[0]
                 perm = (0, 2, 3, 1) if self.dims == 2 else (0, 2, 3, 4, 1)
                 w = self.weight.permute(*perm).reshape(cout, -1)             # tap-major, cin fastest
                 b = self.bias
-                if shuffle2d:                                                # rows (c p1 p2) -> (p1 p2 c)
-                    c = cout // 4
-                    w = w.view(c, 4, -1).transpose(0, 1).reshape(cout, -1)
-                    b = b.view(c, 4).transpose(0, 1).reshape(-1)
+                if shuffle:                                                  # rows (c p1 .. pn) -> (p1 .. pn c)
+                    f = 2 ** shuffle
+                    c = cout // f
+                    w = w.view(c, f, -1).transpose(0, 1).reshape(cout, -1)
+                    b = b.view(c, f).transpose(0, 1).reshape(-1)
                 self._packed = (key, w.contiguous().to(BF16), b.contiguous().to(BF16))
         return self._packed[1], self._packed[2]
 
@@ -59,9 +66,9 @@ class _ConvParams(nn.Module):
         self._packed = None
         return super()._load_from_state_dict(*a, **k)
 
-    def forward(self, x, shuffle2d=False):
+    def forward(self, x, shuffle=0):
         """x NDHWC bf16."""
-        w, b = self.packed(shuffle2d)
+        w, b = self.packed(shuffle)
         return ops.conv3d(x, w, b, causal=False, pad_replicate=False, kernel_t=1 if self.dims == 2 else 3,
                           time_pad_zeros=self.dims == 3)
 
@@ -94,33 +101,47 @@ class ResBlock(nn.Module):                                                   # l
 
 
 class _Upsampler(nn.Module):
-    """nn.Sequential(Conv2d(mid, 4 mid, 3, padding=1), PixelShuffleND(2)) with the reference's key ``upsampler.0``."""
+    """The reference's ``upsampler`` (:83-97) under its key ``upsampler.0``:
+      spatial             nn.Sequential(Conv2d(mid, 4 mid, 3, padding=1), PixelShuffleND(2)), per frame
+      temporal            nn.Sequential(Conv3d(mid, 2 mid, 3, padding=1), PixelShuffleND(1)), then x[:, :, 1:]
+      spatial + temporal  nn.Sequential(Conv3d(mid, 8 mid, 3, padding=1), PixelShuffleND(3)), then x[:, :, 1:]
+    (the trim is forward's, :136-138; it is folded into the shuffle here)."""
 
-    def __init__(self, mid):
+    def __init__(self, mid, spatial=True, temporal=False):
         super().__init__()
-        setattr(self, "0", _ConvParams(mid, 4 * mid, 2))
+        self.spatial, self.temporal = spatial, temporal
+        if temporal:
+            setattr(self, "0", _ConvParams(mid, (8 if spatial else 2) * mid, 3))
+        else:
+            setattr(self, "0", _ConvParams(mid, 4 * mid, 2))
 
     def forward(self, x):
-        return ops.pixel_shuffle2d(getattr(self, "0")(x, shuffle2d=True))
+        conv = getattr(self, "0")
+        if not self.temporal:
+            return ops.pixel_shuffle2d(conv(x, shuffle=2))
+        ps = 2 if self.spatial else 1
+        return ops.pixel_shuffle_nd(conv(x, shuffle=3 if self.spatial else 1), pt=2, ps=ps, drop_first=True)
 
 
 class LatentUpsampler(nn.Module):
     def __init__(self, in_channels: int = 128, mid_channels: int = 512, num_blocks_per_stage: int = 4, dims: int = 3,
                  spatial_upsample: bool = True, temporal_upsample: bool = False):
         super().__init__()
-        if not spatial_upsample or temporal_upsample:
-            if not (spatial_upsample or temporal_upsample):
-                raise ValueError("Either spatial_upsample or temporal_upsample must be True")
-            raise NotImplementedError("ltxmi.LatentUpsampler: only the spatial upsampler is on this path")
+        if not (spatial_upsample or temporal_upsample):
+            raise ValueError("Either spatial_upsample or temporal_upsample must be True")
         if dims not in (2, 3):
             raise NotImplementedError("ltxmi.LatentUpsampler: dims must be 2 or 3")
+        if temporal_upsample and dims != 3:
+            # the reference's dims == 2 branch (:128-147) hands folded 4-D frames to self.upsampler, which a Conv3d cannot take
+            raise NotImplementedError("ltxmi.LatentUpsampler: temporal_upsample needs dims=3 (the reference's dims=2 forward "
+                                      "feeds folded [b*f, c, h, w] frames to the upsampler, which its Conv3d cannot take)")
         self.in_channels, self.mid_channels = in_channels, mid_channels
         self.num_blocks_per_stage, self.dims = num_blocks_per_stage, dims
         self.spatial_upsample, self.temporal_upsample = spatial_upsample, temporal_upsample
         self.initial_conv = _ConvParams(in_channels, mid_channels, dims)
         self.initial_norm = _GroupNormParams(32, mid_channels)
         self.res_blocks = nn.ModuleList([ResBlock(mid_channels, dims=dims) for _ in range(num_blocks_per_stage)])
-        self.upsampler = _Upsampler(mid_channels)
+        self.upsampler = _Upsampler(mid_channels, spatial_upsample, temporal_upsample)
         self.post_upsample_res_blocks = nn.ModuleList(
             [ResBlock(mid_channels, dims=dims) for _ in range(num_blocks_per_stage)])
         self.final_conv = _ConvParams(mid_channels, in_channels, dims)
@@ -146,8 +167,9 @@ class LatentUpsampler(nn.Module):
         return self.final_conv(x)
 
     def forward(self, latent, _stats=None):
-        """latent [b, c, f, h, w] -> [b, c, f, 2h, 2w] (latent_upsampler.py:109-149).  ``_stats`` = (std, mean)
-        fp32 [c]: un_normalize on the way in and normalize on the way out (``_upsample_latents``)."""
+        """latent [b, c, f, h, w] -> [b, c, f, 2h, 2w] (spatial), [b, c, 2f-1, h, w] (temporal) or [b, c, 2f-1, 2h, 2w]
+        (both) (latent_upsampler.py:109-149).  ``_stats`` = (std, mean) fp32 [c]: un_normalize on the way in and
+        normalize on the way out (``_upsample_latents``)."""
         std, mean = _stats if _stats is not None else (None, None)
         x = ops.ncdhw_to_ndhwc(latent.to(BF16), std, mean)
         y = self.forward_ndhwc(x)

@@ -728,6 +728,28 @@ def pixel_shuffle2d(x):
     return out
 
 
+def pixel_shuffle_nd(x, pt, ps, drop_first=False, out=None):
+    """x NDHWC [B,T,H,W,pt*ps*ps*C] (channel (p1 p2 p3 c)) -> [B, pt*T - drop_first, ps*H, ps*W, C]: PixelShuffleND over
+    time (pt = 2) and / or space (ps = 2), and with drop_first the temporal upsampler's ``x[:, :, 1:]`` in the same pass.
+    ``out``: a contiguous tensor of that shape to write into."""
+    _chk_bf16(x, out)
+    if pt not in (1, 2) or ps not in (1, 2) or pt * ps == 1 or (drop_first and pt == 1):
+        raise ValueError("ltxmi.pixel_shuffle_nd: pt, ps in {1, 2}, not both 1; drop_first needs pt = 2")
+    B, T, H, W, Cp = x.shape
+    f = pt * ps * ps
+    if not x.is_contiguous() or Cp % (8 * f):
+        raise ValueError(f"ltxmi.pixel_shuffle_nd: contiguous input with {f}*C channels (C % 8 == 0) expected")
+    drop = int(bool(drop_first))
+    shape = (B, pt * T - drop, ps * H, ps * W, Cp // f)
+    if out is None:
+        out = torch.empty(shape, dtype=BF16, device=x.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"ltxmi.pixel_shuffle_nd: `out` must be a contiguous {list(shape)} tensor on x's device")
+    check(lib.ltxmi_pixel_shuffle_nd_ndhwc_bf16(_ptr(x), _ptr(out), B, T, H, W, Cp // f, pt, ps, drop, _stream()),
+          "ltxmi_pixel_shuffle_nd_ndhwc_bf16")
+    return out
+
+
 def adain_filter(latents, reference, factor=1.0):
     """latents [B,C,...], reference [B,C,...] (NCDHW, fp32 or bf16): per-(b,c) statistics transfer."""
     if latents.dtype != reference.dtype or latents.dtype not in (BF16, torch.float32):
