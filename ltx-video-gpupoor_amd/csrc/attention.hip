@@ -76,17 +76,10 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
     const int r = lane & 31;      // query column of this lane
     const int hh = lane >> 5;     // which 4-row group of every 8 accumulator rows
 
-    // ---- XCD-aware work id (bijective chunking, see gemm.hip)
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, qn = nwg >> 3, rn = nwg & 7;
-    const int work = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (orig >> 3);
-    const int bh = work / p.q_tiles, qt = work % p.q_tiles;
-    const int b = bh / p.H, head = bh % p.H;
-
-    const uint16_t* qb = p.q + (int64_t)b * p.q_sb + head * DH;
-    const uint16_t* kb_ = p.k + (int64_t)b * p.k_sb + head * DH;
-    const uint16_t* vb = p.v + (int64_t)b * p.v_sb + head * DH;
-    uint16_t* ob = p.o + (int64_t)b * p.o_sb + head * DH;
+    const AttnItem item = attn_item<DH>(p);
+    const int b = item.b, head = item.head, qt = item.tile;
+    const uint16_t *qb = item.q, *kb_ = item.k, *vb = item.v;
+    uint16_t* ob = item.o;
     const float* biasb = HAS_BIAS ? p.bias + (int64_t)b * p.bias_sb : nullptr;
 
     // ---- Q^T fragments (B operand): lane (r, hh), k-step s holds Q[q][16 s + 8 hh .. +7]
@@ -98,7 +91,9 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
         const int q_ld = q_row[i] < p.Lq ? q_row[i] : p.Lq - 1;
         // optional: q is the raw projection output; q_norm (RMSNorm over all H * dh channels from the projection GEMM's
         // partial sums of squares, x weight) and the interleaved-pair RoPE are applied here, with the arithmetic of
-        // rmsnorm_rope_kernel (rowops.hip): fp32, one rounding to bf16 at the end (see attention_pipe.hip)
+        // rmsnorm_rope_kernel (rowops.hip): fp32, one rounding to bf16 at the end.  Kept here, k-step by k-step between the
+        // loads, and not attn_finish_q (attention.h): through that helper hipcc fused the multiplies and adds of this kernel
+        // differently and 24 of 123 compared outputs moved in the last bit.
         const float rstd = p.q_on_load() ? p.q_row_rstd(b, q_ld, p.H * DH) : 0.f;
 #pragma unroll
         for (int s = 0; s < C::KSTEPS; ++s) {
@@ -199,24 +194,14 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
     for (int kb = 0; kb < 2; ++kb) k_rd[kb] = (32 * kb + r) * C::ROW_BYTES;
     const int k_sw0 = C::k_swz(r);                 // swz(32 + r) == swz(r) for both head dims
     // V^T (A operand of PV) via transposed reads: block rows 16 s' + 4 hh + q (+8), cols 32 db + r
-    const int g16 = lane >> 4, i16 = lane & 15;
-    const int v_rd = C::TILE_BYTES + (4 * (g16 >> 1) + (i16 >> 2)) * 64 + (16 * (g16 & 1) + 4 * (i16 & 3)) * 2;
+    const int v_rd = C::TILE_BYTES + attn_vt_offset(lane);
 
     f32x16 oT[QB][C::DBLK];
     float m_run[QB];           // running max: raw scores (no bias) or scaled+biased log2 domain (bias)
-    // Row sums on the matrix pipe (the VALU is the co-limiting pipe at head_dim 64): the P^T fragment
-    // of the 32x32x16 PV product, re-read as the B operand of a 16x16x32 MFMA, puts query (l & 15)
-    // [+16 for odd 16-lane groups] on the column and this lane's 8 keys in k-group (l >> 4).  With
-    // A = 1 on (row 0, even k-groups) and (row 1, odd k-groups), D[0][n] = sum over the tile's keys of
-    // P[query n] and D[1][n] = the same for query n + 16: lanes 0..15 hold them in registers 0 and 1.
-    // One 16-cycle MFMA per 16 keys replaces 8 v_add per lane; 4 accumulator registers per block.
+    // Row sums on the matrix pipe (attn_ones_operand; the VALU is the co-limiting pipe at head_dim 64): one 16-cycle MFMA
+    // per 16 keys replaces 8 v_add per lane; 4 accumulator registers per block.
     f32x4 lT[QB];
-    bf16x8 ones;
-    {
-        const bool on = ((lane & 15) == 0 && ((lane >> 4) & 1) == 0) || ((lane & 15) == 1 && ((lane >> 4) & 1) == 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ones[e] = on ? (__bf16)1.0f : (__bf16)0.0f;
-    }
+    const bf16x8 ones = attn_ones_operand(lane);
     bf16x8 kaug, maug[QB];      // FOLD: A operand (ones at k = 0, 1) and B operand (-m as hi + lo bf16)
 #pragma unroll
     for (int e = 0; e < 8; ++e) kaug[e] = (hh == 0 && e < 2) ? (__bf16)1.0f : (__bf16)0.0f;
@@ -299,10 +284,7 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
                 const float a = max3(l1[1], l1[2], l1[3]), b2 = max3(l1[4], l1[5], l1[6]), c2 = max3(l1[7], l1[8], l1[9]);
                 mt = fmaxf(max3(a, b2, c2), l1[10]);
             }
-            {
-                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-                mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-            }
+            mt = attn_lane_half_max(mt);
             float nmoff = 0.f;                                   // -(max in the exponent's domain)
             if (FOLD) {
                 // sT already holds x - m_run.  The max moved iff some element is > 0 (always on the
@@ -371,14 +353,7 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
                 lT[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[sp], lT[i], 0, 0, 0);
 #pragma unroll
                 for (int d = 0; d < C::DBLK; ++d) {
-                    const char* base = s + v_rd + (2 * sp * C::DBLK + d) * 512;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) s16x4*)(base));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) s16x4*)(base + C::DBLK * 512));
-                    typedef __attribute__((ext_vector_type(8))) short s16x8;
-                    const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const bf16x8 vf = __builtin_bit_cast(bf16x8, both);
+                    const bf16x8 vf = attn_vt_fragment<DH>(s + v_rd + (2 * sp * C::DBLK + d) * 512);
                     oT[i][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[sp], oT[i][d], 0, 0, 0);
                 }
             }
@@ -447,14 +422,9 @@ __global__ __launch_bounds__(256, (QB == 2 || DH == 128) ? 2 : 1) void attn_fwd_
 template <int DH, bool HAS_BIAS, int QB>
 static int launch(AttnParams p, hipStream_t stream) {
     using C = AttnCfg<DH>;
-    auto kern = attn_fwd_kernel<DH, HAS_BIAS, QB>;
     static unsigned long long lds_done = 0;
-    if (const int rc = reserve_lds((const void*)kern, C::SMEM, &lds_done, "ltxmi_attention_fwd_bf16")) return rc;
     const int q_per_wg = Q_PER_WG * QB;
-    p.q_tiles = (p.Lq + q_per_wg - 1) / q_per_wg;
-    const int64_t grid = (int64_t)p.B * p.H * p.q_tiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::SMEM, stream, p);
-    return check_launch("ltxmi_attention_fwd_bf16");
+    return attn_launch(attn_fwd_kernel<DH, HAS_BIAS, QB>, C::SMEM, &lds_done, p, (p.Lq + q_per_wg - 1) / q_per_wg, stream);
 }
 
 // Which kernel runs a shape (sizes positive, head_dim 64 or 128): ltxmi_attention_fwd_bf16 launches it, ltxmi_attention_kernel_id

@@ -55,9 +55,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
     const int r = lane & 31, hh = lane >> 5;
 
     // ---- XCD-aware work id (bijective chunking): the row groups of a (batch, head) run on one XCD and share its K / V in L2
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, qn = nwg >> 3, rn = nwg & 7;
-    const int work = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (orig >> 3);
+    const int work = xcd_work_id();
     const int bh = work / groups, grp = work % groups;
     const int b = bh / p.H, head = bh % p.H;
     const int row_begin = grp * rows_per_group;
@@ -145,8 +143,9 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
         for (int s = 0; s < 4; ++s) qraw[s] = *(const bf16x8*)(qb + (int64_t)q_ld * p.q_sl + 16 * s + 8 * hh);
         if (p.q_on_load()) q_rstd = p.q_row_rstd(b, q_ld, p.H * DH);
     };
-    // qraw -> qf; optional q_norm (+ RoPE) with rmsnorm_rope_kernel's arithmetic (see attention_pipe.hip): x * rstd * weight,
-    // interleaved-pair rotation, ONE rounding to bf16
+    // qraw -> qf; optional q_norm (+ RoPE) with rmsnorm_rope_kernel's arithmetic: x * rstd * weight, interleaved-pair
+    // rotation, ONE rounding to bf16.  (attn_finish_q of attention.h written out, with the weights from LDS: as a helper it
+    // changed this kernel's generated code.)
     auto finish_q = [&]() {
         if (p.q_on_load()) {
             const int64_t trow = (int64_t)b * p.rope_sb + (int64_t)q_ld * p.rope_sl;
@@ -238,10 +237,7 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
         if (it + 1 < n_it) finish_q();
         if (it + 2 < n_it) load_q(it + 2);
         group_max(NG - 1);
-        {
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-            mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-        }
+        mt = attn_lane_half_max(mt);
         const float nmc = -mt * c;                           // P = 2^(c s' - c m): one FMA per score
         // (every key masked: the reference's softmax over a row of -10000s is uniform; here the bias is finite for every
         //  real key, so mt is finite whenever Lk >= 1)
@@ -257,17 +253,11 @@ __global__ __launch_bounds__(256, 2) void attn_cross_kernel(AttnParams p, int gr
         // fragments of the NEXT step requested before them and one quarter of the NEXT tile's exp2 / cvt (8 scores -> one P
         // fragment) behind them.  (Left to hipcc every PV MFMA waited out the LDS latency of the transposed reads issued right
         // in front of it.)
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
         auto read_v = [&](int t, int sp, bf16x8 (&dst)[2]) {
             const char* vs = smem + V_OFF + t * TILE_BYTES + v_rd;
 #pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                const char* base = vs + (2 * sp * 2 + d) * 512;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 2 * 512));
-                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                dst[d] = __builtin_bit_cast(bf16x8, both);
-            }
+            for (int d = 0; d < 2; ++d)
+                dst[d] = attn_vt_fragment<DH>(vs + (2 * sp * 2 + d) * 512);
         };
         // P fragment sp' of tile t: scores 8 h2 .. 8 h2 + 7 of key block kb, sp' = 2 kb + h2
         auto make_p = [&](int t, int sp2, bf16x8& dst) {
@@ -345,25 +335,19 @@ int launch_attn_cross(AttnParams p, hipStream_t stream) {
     int rows = (p.Lq + groups - 1) / groups;
     rows = (rows + cross::ROWS_PER_IT - 1) / cross::ROWS_PER_IT * cross::ROWS_PER_IT;
     groups = (p.Lq + rows - 1) / rows;
-    const int64_t grid = (int64_t)bh * groups;
     const int nt = (p.Lk + cross::KV_TILE - 1) / cross::KV_TILE;
 #define LTXMI_XATTN_LAUNCH(N)                                                                                              \
     {                                                                                                                      \
         static unsigned long long lds_done = 0;                                                                            \
-        if (const int rc = reserve_lds((const void*)cross::attn_cross_kernel<N>, cross::SMEM, &lds_done,                   \
-                                       "ltxmi_attention_fwd_bf16"))                                                        \
-            return rc;                                                                                                     \
-        hipLaunchKernelGGL(cross::attn_cross_kernel<N>, dim3((unsigned)grid), dim3(256), cross::SMEM, stream, p, groups,   \
-                           rows, n_cu);                                                                                    \
+        return attn_launch(cross::attn_cross_kernel<N>, cross::SMEM, &lds_done, p, groups, stream, groups, rows, n_cu);    \
     }
     switch (nt) {
-        case 1: LTXMI_XATTN_LAUNCH(1) break;
-        case 2: LTXMI_XATTN_LAUNCH(2) break;
-        case 3: LTXMI_XATTN_LAUNCH(3) break;
-        default: LTXMI_XATTN_LAUNCH(4) break;
+        case 1: LTXMI_XATTN_LAUNCH(1)
+        case 2: LTXMI_XATTN_LAUNCH(2)
+        case 3: LTXMI_XATTN_LAUNCH(3)
+        default: LTXMI_XATTN_LAUNCH(4)
     }
 #undef LTXMI_XATTN_LAUNCH
-    return check_launch("ltxmi_attention_fwd_bf16");
 }
 
 }  // namespace ltxmi

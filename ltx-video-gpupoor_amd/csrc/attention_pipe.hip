@@ -117,9 +117,7 @@ __device__ __forceinline__ void segment(Blk& X, Blk& Y, bf16x8 (&kf)[8], const c
             }
             l1[10] = max3(X.s[0][15], X.s[1][15], l1[0]);
             const float a = max3(l1[1], l1[2], l1[3]), b2 = max3(l1[4], l1[5], l1[6]), c2 = max3(l1[7], l1[8], l1[9]);
-            mt = fmaxf(max3(a, b2, c2), l1[10]);
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-            mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+            mt = attn_lane_half_max(fmaxf(max3(a, b2, c2), l1[10]));
         }
         const float m_new = fmaxf(X.m, mt);
         // the O-wide rescale is a real wave-uniform branch
@@ -143,7 +141,6 @@ __device__ __forceinline__ void segment(Blk& X, Blk& Y, bf16x8 (&kf)[8], const c
     // softmax (2 exp2, 1 cvt_pk; + 2 v_mul for raw scores; the exact form: + 2 v_sub / v_fma) each
     bf16x8 vf[8];
     float pp0 = 0.f, pp1 = 0.f;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         if (j < 8) {
@@ -154,11 +151,7 @@ __device__ __forceinline__ void segment(Blk& X, Blk& Y, bf16x8 (&kf)[8], const c
             }
             Y.s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[j], Y.q[s], Y.s[kb], 0, 0, 0);
             // V^T fragment of PV MFMA j (k-step sp = j >> 1, head-dim block d = j & 1)
-            const char* base = vs + L.v_rd + (2 * (j >> 1) * 2 + (j & 1)) * 512;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 2 * 512));
-            const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            vf[j] = __builtin_bit_cast(bf16x8, both);
+            vf[j] = attn_vt_fragment<DH>(vs + L.v_rd + (2 * (j >> 1) * 2 + (j & 1)) * 512);
         } else {
             const int jj = j - 8, sp = jj >> 1, d = jj & 1;
             Y.o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[jj], __builtin_bit_cast(bf16x8, Y.pf[sp]), Y.o[d], 0, 0, 0);
@@ -206,29 +199,12 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
     L.r = L.lane & 31;
     L.hh = L.lane >> 5;
 
-    // ---- XCD-aware work id (bijective chunking): an XCD walks whole (batch, head) pairs
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, qn = nwg >> 3, rn = nwg & 7;
-    const int work = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (orig >> 3);
-    const int bh = work / p.q_tiles, qt = work % p.q_tiles;
-    const int b = bh / p.H, head = bh % p.H;
+    const AttnItem item = attn_item<DH>(p);
+    const int qt = item.tile;
 
-    const uint16_t* qb = p.q + (int64_t)b * p.q_sb + head * DH;
-    const uint16_t* kb_ = p.k + (int64_t)b * p.k_sb + head * DH;
-    const uint16_t* vb = p.v + (int64_t)b * p.v_sb + head * DH;
-    uint16_t* ob = p.o + (int64_t)b * p.o_sb + head * DH;
-
-    // ---- LDS-DMA sources.  One descriptor per operand (base = this (batch, head)'s first row,
-    // num_records = up to the end of its last row): key rows past Lk are out of range and arrive as zeros.
-    // The DMA is issued from inline asm: for a builtin LDS-DMA hipcc puts s_waitcnt vmcnt(0) in front of the
-    // next transposed LDS read (it cannot tell the slots apart), which would drain the ring every segment.
-    // Completion is counted by hand instead (vmcnt(4) at the end of an iteration, then the barrier).
-    auto make_desc = [](const void* base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, (uint32_t)bytes, 0x00020000u};
-    };
-    const u32x4 k_desc = make_desc(kb_, ((int64_t)(p.Lk - 1) * p.k_sl + DH) * 2);
-    const u32x4 v_desc = make_desc(vb, ((int64_t)(p.Lk - 1) * p.v_sl + DH) * 2);
+    // ---- LDS-DMA sources (attention.h; completion is counted with vmcnt(4) at the end of an iteration)
+    const u32x4 k_desc = attn_kv_desc<DH>(item.k, p.Lk, p.k_sl);
+    const u32x4 v_desc = attn_kv_desc<DH>(item.v, p.Lk, p.v_sl);
     // wave w moves pieces 2w, 2w+1 (8 key rows = 1 KiB each) of every K and V tile.
     //   K image: row r, 16-byte chunk c at slot c ^ ((r >> 1) & 7); lane l of a piece writes row l >> 3, slot l & 7
     //   V image: [8 key][32 col] sub-tiles of 512 B; lane l writes sub-tile l >> 5 (column half), key (l >> 2) & 7, chunk l & 3
@@ -261,26 +237,14 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
             : "v"(voff0), "v"(voff1), "s"(lds_addr), "s"(desc)
             : "memory", "scc");
     };
-    auto dma1 = [&](const u32x4& desc, uint32_t lds_addr, uint32_t voff) {
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(voff), "s"(lds_addr), "s"(desc)
-            : "memory");
-    };
     // piece i (0 / 1) of this wave's share of K tile t / V tile t
     auto dma_k1 = [&](int t, int i) {
         const uint32_t dst = lds0 + (uint32_t)((t & (RING - 1)) * TILE_BYTES + (2 * wave + i) * 1024);
-        dma1(k_desc, dst, k_voff[i] + (uint32_t)t * k_tile_step);
+        attn_lds_dma(k_desc, dst, k_voff[i] + (uint32_t)t * k_tile_step);
     };
     auto dma_v1 = [&](int t, int i) {
         const uint32_t dst = lds0 + (uint32_t)((RING + (t & (RING - 1))) * TILE_BYTES + (2 * wave + i) * 1024);
-        dma1(v_desc, dst, v_voff[i] + (uint32_t)t * v_tile_step);
+        attn_lds_dma(v_desc, dst, v_voff[i] + (uint32_t)t * v_tile_step);
     };
     auto dma_k = [&](int t) {
         const uint32_t dst = lds0 + (uint32_t)((t & (RING - 1)) * TILE_BYTES + 2 * wave * 1024);
@@ -299,54 +263,21 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
     L.k_rd[0] = L.r * ROW_BYTES;
     L.k_rd[1] = (32 + L.r) * ROW_BYTES;
     L.k_sw0 = (L.r >> 1) & 7;                       // swz(32 + r) == swz(r)
-    {
-        const int g16 = L.lane >> 4, i16 = L.lane & 15;
-        L.v_rd = (4 * (g16 >> 1) + (i16 >> 2)) * 64 + (16 * (g16 & 1) + 4 * (i16 & 3)) * 2;
-    }
+    L.v_rd = attn_vt_offset(L.lane);
 
     // ---- state.  Block B's "pending" P of tile -1 is zero and multiplies V slot 3, which is zero-filled.
     Blk A, Bk;
-    bf16x8 ones;
-    {
-        const bool on = ((L.lane & 15) == 0 && ((L.lane >> 4) & 1) == 0) || ((L.lane & 15) == 1 && ((L.lane >> 4) & 1) == 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ones[e] = on ? (__bf16)1.0f : (__bf16)0.0f;
-    }
+    const bf16x8 ones = attn_ones_operand(L.lane);
     const float c = p.scale_log2e;
     auto init = [&](Blk& X, int blk) {
         const int row = qt * Q_PER_WG + wave * 64 + 32 * blk + L.r;
         const int q_ld = row < p.Lq ? row : p.Lq - 1;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) X.q[s] = *(const bf16x8*)(qb + (int64_t)q_ld * p.q_sl + 16 * s + 8 * L.hh);
-        if (QSCALED) {                     // == p.q_on_load(): the launcher picks the instance by it
-            // fused K1: q is the raw projection output.  q_norm (RMSNorm over all H * dh channels, attention.py:478-479,
-            // 1040-1041) from the row's factor (finalised per row by k's pass, or the projection GEMM's partial sums of
-            // squares), x weight, then the interleaved-pair RoPE on the flat channel axis (:960-975, 1053-1055) -- the
-            // arithmetic of rmsnorm_rope_kernel (rowops.hip), one rounding to bf16 at the end.
-            const float rstd = p.q_row_rstd(b, q_ld, p.H * DH);
-            const int64_t trow = (int64_t)b * p.rope_sb + (int64_t)q_ld * p.rope_sl;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int col = head * DH + 16 * s + 8 * L.hh;
-                const bf16x8 wv = *(const bf16x8*)(p.q_w + col);
-                float o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (float)X.q[s][e] * rstd * (float)wv[e];
-                if (p.rope_cos) {
-                    const bf16x8 cv = *(const bf16x8*)(p.rope_cos + trow + col), sv = *(const bf16x8*)(p.rope_sin + trow + col);
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const float r0 = o[e] * (float)cv[e] - o[e + 1] * (float)sv[e];
-                        const float r1 = o[e + 1] * (float)cv[e + 1] + o[e] * (float)sv[e + 1];
-                        o[e] = r0;
-                        o[e + 1] = r1;
-                    }
-                }
-                // (x softmax_scale * log2(e) before the one rounding: the scores leave the matrix pipe in bits)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) X.q[s][e] = (__bf16)(QSCALED ? o[e] * c : o[e]);
-            }
-        }
+        for (int s = 0; s < 4; ++s) X.q[s] = *(const bf16x8*)(item.q + (int64_t)q_ld * p.q_sl + 16 * s + 8 * L.hh);
+        // QSCALED == p.q_on_load() (the launcher picks the instance by it): q is the raw projection output (fused K1:
+        // attention.py:478-479, 960-975, 1040-1041, 1053-1055 of the reference) and is finished here, x softmax_scale * log2(e)
+        // before its one rounding: the scores leave the matrix pipe in bits
+        if (QSCALED) attn_finish_q<DH>(p, item, q_ld, L.hh, p.q_row_rstd(item.b, q_ld, p.H * DH), c, X.q);
         X.m = -INFINITY;
         X.l = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -453,58 +384,30 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
         const char* vs = vring + ((nt - 1) & 3) * TILE_BYTES;
 #pragma unroll
         for (int sp = 0; sp < 4; ++sp) Bk.l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, __builtin_bit_cast(bf16x8, Bk.pf[sp]), Bk.l, 0, 0, 0);
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
 #pragma unroll
         for (int sp = 0; sp < 4; ++sp)
 #pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                const char* base = vs + L.v_rd + (2 * sp * 2 + d) * 512;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 2 * 512));
-                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                Bk.o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, both), __builtin_bit_cast(bf16x8, Bk.pf[sp]), Bk.o[d], 0, 0, 0);
-            }
+            for (int d = 0; d < 2; ++d)
+                Bk.o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(attn_vt_fragment<DH>(vs + L.v_rd + (2 * sp * 2 + d) * 512),
+                                                                  __builtin_bit_cast(bf16x8, Bk.pf[sp]), Bk.o[d], 0, 0, 0);
     }
     // the out-of-range pieces of tiles >= nt are still landing (as zeros): drain them before the rings are reused (as the
     // output scratch, or by the redo's stream); then agree on the redo
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (!REDO) {
-    bool outgrown = false;
-    if (t_exact < nt && !wave_idle) {
-        // a row sum or an accumulator of magnitude >= 2^100 (or inf / NaN: the test is on the exponent bits, the file is
-        // built with -fno-honor-nans) = a score too large for the fixed reference (not only overflow: 1 / l for l > 2^126 is
-        // a denormal and flushes to zero); a row sum below 2^-100 (or 0) = a row whose scores all underflowed.
-        constexpr uint32_t OUTGROWN_EXP = (127u + 100u) << 23, VANISHED_EXP = (127u - 100u) << 23;
-        uint32_t worst = 0;
-        auto scan = [&](const Blk& X) {
-            worst |= (uint32_t)((__float_as_uint(X.l[0]) & 0x7f800000u) >= OUTGROWN_EXP);
-            worst |= (uint32_t)((__float_as_uint(X.l[1]) & 0x7f800000u) >= OUTGROWN_EXP);
-            // (the row sums live in lanes 0..15, registers 0 / 1; a sum of 0 has exponent bits 0)
-            if (L.lane < 16) {
-                worst |= (uint32_t)((__float_as_uint(X.l[0]) & 0x7f800000u) < VANISHED_EXP);
-                worst |= (uint32_t)((__float_as_uint(X.l[1]) & 0x7f800000u) < VANISHED_EXP);
-            }
-#pragma unroll
-            for (int d = 0; d < 2; ++d)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) worst |= (uint32_t)((__float_as_uint(X.o[d][e]) & 0x7f800000u) >= OUTGROWN_EXP);
-        };
-        scan(A);
-        scan(Bk);
-        outgrown = __any(worst != 0);
-    }
-    if (outgrown && L.lane == 0) *redo_flag = 1;
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    const int redo = *redo_flag;
-    __builtin_amdgcn_s_barrier();
-    if (redo != 0) return true;
+        // scores too large for the fixed reference, or a row whose scores all underflowed
+        bool outgrown = false;
+        if (t_exact < nt && !wave_idle)
+            outgrown = __any(attn_out_of_range<true>(attn_out_of_range<true>(0u, A.l, A.o, L.lane), Bk.l, Bk.o, L.lane) != 0);
+        if (attn_agree_redo(redo_flag, outgrown, L.lane) != 0) return true;
     } else {
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    // ---- epilogue: O = O^T / l, through a per-wave LDS scratch so that rows leave whole (attention.hip)
+    // ---- epilogue: O = O^T / l, through a per-wave LDS scratch so that rows leave whole.  Not a helper shared with the other
+    // kernels: with this body moved into force-inlined functions (several shapes tried) the spill counts of all four instances
+    // of this kernel changed (e.g. 16 -> 17 / 22 -> 21 spilled VGPRs in the normal runs).
     auto store = [&](Blk& X, int blk) {
         const float l0 = __shfl(X.l[0], L.r & 15, 64), l1 = __shfl(X.l[1], L.r & 15, 64);
         const float lrow = (L.r & 16) ? l1 : l0;
@@ -512,7 +415,7 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
         if (p.lse != nullptr) {
             // (wave-uniform) the steady form's reference is 0; the exact form's is the running maximum X.m (bits if QSCALED)
             const int row = qt * Q_PER_WG + wave * 64 + 32 * blk + L.r;
-            if (L.hh == 0 && row < p.Lq) p.store_lse(b, head, row, REDO ? (QSCALED ? X.m : X.m * c) : 0.f, lrow, false);
+            if (L.hh == 0 && row < p.Lq) p.store_lse(item.b, item.head, row, REDO ? (QSCALED ? X.m : X.m * c) : 0.f, lrow, false);
         }
         char* scr = smem + (wave * 2 + blk) * (32 * ROW_BYTES);
 #pragma unroll
@@ -530,7 +433,7 @@ __device__ __forceinline__ bool attn_pipe_item(const AttnParams& p, const int ti
         for (int t = 0; t < 4; ++t) {
             const int row = t * 8 + (L.lane >> 3), chunk = L.lane & 7;
             const u32x4 w = *(const u32x4*)(scr + row * ROW_BYTES + ((chunk ^ (row & 7)) << 4));
-            if (q0 + row < p.Lq) *(u32x4*)(ob + p.o_row(q0 + row) + chunk * 8) = w;
+            if (q0 + row < p.Lq) *(u32x4*)(item.o + p.o_row(q0 + row) + chunk * 8) = w;
         }
     };
     store(A, 0);
@@ -576,11 +479,7 @@ int launch_attn_pipe(AttnParams p, hipStream_t stream) {
     auto kern = p.force_exact ? (qscaled ? pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, true, true> : pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, false, true>)
                               : (qscaled ? pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, true, false> : pipe::attn_pipe_kernel<LTXMI_ATTN_PIPE_OCC, false, false>);
     static unsigned long long lds_done[4] = {0, 0, 0, 0};
-    if (const int rc = reserve_lds((const void*)kern, pipe::SMEM + 16, &lds_done[(p.force_exact ? 2 : 0) + qscaled], "ltxmi_attention_fwd_bf16")) return rc;
-    p.q_tiles = (p.Lq + pipe::Q_PER_WG - 1) / pipe::Q_PER_WG;
-    const int64_t grid = (int64_t)p.B * p.H * p.q_tiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), pipe::SMEM + 16, stream, p);
-    return check_launch("ltxmi_attention_fwd_bf16");
+    return attn_launch(kern, pipe::SMEM + 16, &lds_done[(p.force_exact ? 2 : 0) + qscaled], p, (p.Lq + pipe::Q_PER_WG - 1) / pipe::Q_PER_WG, stream);
 }
 
 }  // namespace ltxmi

@@ -65,12 +65,7 @@ __device__ __forceinline__ bf16x8 kread(const char* slot, const Lane& L, int i) 
 }
 __device__ __forceinline__ bf16x8 vread(const char* slot, const Lane& L, int i) {
     // V^T fragment of PV MFMA i: k-step sp = i >> 2 (keys 16 sp ..), head-dim block d = i & 3
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    const char* base = slot + L.v_rd + ((2 * (i >> 2)) * 4 + (i & 3)) * 512;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * 512));
-    const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, both);
+    return attn_vt_fragment<DH>(slot + L.v_rd + ((2 * (i >> 2)) * 4 + (i & 3)) * 512);
 }
 
 // Register placement is pinned by hand.  The state of two blocks is ~300 registers; what only the matrix pipe touches --
@@ -199,8 +194,7 @@ __device__ __forceinline__ void segment(Blk& X, Blk& Y, bf16x8 (&kq)[4], const c
     }
     X.pf[3][3] = pack_bf16(pa, pb);
     if (EXACT) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-        Y.mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+        Y.mt = attn_lane_half_max(mt);
     }
 }
 
@@ -216,26 +210,12 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
     L.r = L.lane & 31;
     L.hh = L.lane >> 5;
 
-    // ---- XCD-aware work id (bijective chunking): an XCD walks whole (batch, head) pairs
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, qn = nwg >> 3, rn = nwg & 7;
-    const int work = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (orig >> 3);
-    const int bh = work / p.q_tiles, qt = work % p.q_tiles;
-    const int b = bh / p.H, head = bh % p.H;
+    const AttnItem item = attn_item<DH>(p);
+    const int qt = item.tile;
 
-    const uint16_t* qb = p.q + (int64_t)b * p.q_sb + head * DH;
-    const uint16_t* kb_ = p.k + (int64_t)b * p.k_sb + head * DH;
-    const uint16_t* vb = p.v + (int64_t)b * p.v_sb + head * DH;
-    uint16_t* ob = p.o + (int64_t)b * p.o_sb + head * DH;
-
-    // ---- LDS-DMA sources (attention_pipe.hip): one descriptor per operand, key rows past Lk arrive as zeros; issued from
-    // inline asm so that hipcc does not drain the ring in front of every transposed LDS read
-    auto make_desc = [](const void* base, int64_t bytes) {
-        const uint64_t a = (uint64_t)base;
-        return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, (uint32_t)bytes, 0x00020000u};
-    };
-    const u32x4 k_desc = make_desc(kb_, ((int64_t)(p.Lk - 1) * p.k_sl + DH) * 2);
-    const u32x4 v_desc = make_desc(vb, ((int64_t)(p.Lk - 1) * p.v_sl + DH) * 2);
+    // ---- LDS-DMA sources (attention.h; completion is counted with vmcnt(8) at the end of an iteration)
+    const u32x4 k_desc = attn_kv_desc<DH>(item.k, p.Lk, p.k_sl);
+    const u32x4 v_desc = attn_kv_desc<DH>(item.v, p.Lk, p.v_sl);
     // wave w moves pieces 4w .. 4w+3 (1 KiB each) of every K and V tile.
     //   K piece P: rows 4P .. 4P+3; lane l writes row l >> 4, slot l & 15 <- source chunk (l & 15) ^ (row & 15)
     //   V piece P: keys 8 (P >> 1) .. + 7, columns 64 (P & 1) .. + 63 = two adjacent sub-tiles (1 KiB, contiguous in the
@@ -254,26 +234,14 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
     }
     const uint32_t k_tile_step = (uint32_t)(KV_TILE * (int)p.k_sl * 2), v_tile_step = (uint32_t)(KV_TILE * (int)p.v_sl * 2);
     const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
-    auto dma1 = [&](const u32x4& desc, uint32_t lds_addr, uint32_t voff) {
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(voff), "s"(lds_addr), "s"(desc)
-            : "memory");
-    };
     // piece i (0..3) of this wave's share of K tile t / V tile t
     auto dma_k1 = [&](int t, int i) {
         const uint32_t dst = lds0 + (uint32_t)((t & (RING - 1)) * TILE_BYTES + (PIECES * wave + i) * 1024);
-        dma1(k_desc, dst, k_voff[i] + (uint32_t)t * k_tile_step);
+        attn_lds_dma(k_desc, dst, k_voff[i] + (uint32_t)t * k_tile_step);
     };
     auto dma_v1 = [&](int t, int i) {
         const uint32_t dst = lds0 + (uint32_t)((RING + (t & (RING - 1))) * TILE_BYTES + (PIECES * wave + i) * 1024);
-        dma1(v_desc, dst, v_voff[i] + (uint32_t)t * v_tile_step);
+        attn_lds_dma(v_desc, dst, v_voff[i] + (uint32_t)t * v_tile_step);
     };
     auto dma_k = [&](int t) {
 #pragma unroll
@@ -288,49 +256,18 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
     // ---- per-lane LDS read offsets
 #pragma unroll
     for (int s8 = 0; s8 < 8; ++s8) L.koff[s8] = L.r * ROW_BYTES + (((2 * s8 + L.hh) ^ (L.r & 15)) << 4);   // swz(32 + r) == swz(r)
-    {
-        const int g16 = L.lane >> 4, i16 = L.lane & 15;
-        L.v_rd = (4 * (g16 >> 1) + (i16 >> 2)) * 64 + (16 * (g16 & 1) + 4 * (i16 & 3)) * 2;
-    }
+    L.v_rd = attn_vt_offset(L.lane);
 
     // ---- state.  Block B's "pending" P of tile -1 is zero and multiplies V slot 3, which is zero-filled.
     Blk A, Bk;
-    bf16x8 ones;
-    {
-        const bool on = ((L.lane & 15) == 0 && ((L.lane >> 4) & 1) == 0) || ((L.lane & 15) == 1 && ((L.lane >> 4) & 1) == 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ones[e] = on ? (__bf16)1.0f : (__bf16)0.0f;
-    }
+    const bf16x8 ones = attn_ones_operand(L.lane);
     auto init = [&](Blk& X, int blk) {
         const int row = qt * Q_PER_WG + wave * 64 + 32 * blk + L.r;
         const int q_ld = row < p.Lq ? row : p.Lq - 1;
 #pragma unroll
-        for (int s = 0; s < NS; ++s) X.q[s] = *(const bf16x8*)(qb + (int64_t)q_ld * p.q_sl + 16 * s + 8 * L.hh);
-        if (p.q_on_load()) {
-            // fused q_norm (+ RoPE) on load: the arithmetic of rmsnorm_rope_kernel (rowops.hip), see attention_pipe.hip
-            const float rstd = p.q_row_rstd(b, q_ld, p.H * DH);
-            const int64_t trow = (int64_t)b * p.rope_sb + (int64_t)q_ld * p.rope_sl;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int col = head * DH + 16 * s + 8 * L.hh;
-                const bf16x8 wv = *(const bf16x8*)(p.q_w + col);
-                float o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (float)X.q[s][e] * rstd * (float)wv[e];
-                if (p.rope_cos) {
-                    const bf16x8 cv = *(const bf16x8*)(p.rope_cos + trow + col), sv = *(const bf16x8*)(p.rope_sin + trow + col);
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        const float r0 = o[e] * (float)cv[e] - o[e + 1] * (float)sv[e];
-                        const float r1 = o[e + 1] * (float)cv[e + 1] + o[e] * (float)sv[e + 1];
-                        o[e] = r0;
-                        o[e + 1] = r1;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) X.q[s][e] = (__bf16)o[e];
-            }
-        }
+        for (int s = 0; s < NS; ++s) X.q[s] = *(const bf16x8*)(item.q + (int64_t)q_ld * p.q_sl + 16 * s + 8 * L.hh);
+        // q finished on load (q_norm, RoPE; the raw scores are scaled in the softmax: post = 1)
+        if (p.q_on_load()) attn_finish_q<DH>(p, item, q_ld, L.hh, p.q_row_rstd(item.b, q_ld, p.H * DH), 1.0f, X.q);
         X.m = -INFINITY;
         X.mt = -INFINITY;
         X.l = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -395,8 +332,7 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
                     }
                     mt = fmaxf(mt, A.s[kb2][e]);
                 }
-            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-            A.mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+            A.mt = attn_lane_half_max(mt);
         }
 
         // iteration t: segment 1 produces block B's scores of tile t, segment 2 block A's of tile t + 1 (tile nt: every key
@@ -433,36 +369,19 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         bool outgrown = false;
         if (attempt == 0 && t_exact < nt) {
-            // did a score outgrow its row's fixed reference?  Then a row sum or an accumulator has magnitude >= 2^100 (or is
-            // inf / NaN: the test is on the exponent bits, the file is built with -fno-honor-nans).  Not only overflow:
-            // 1 / l for l > 2^126 is a denormal and flushes to zero; a legitimate l is at most (keys) x 2^(a few bits).
-            constexpr uint32_t OUTGROWN_EXP = (127u + 100u) << 23;
+            // did a score outgrow its row's fixed reference?
             settle_o(A.o);
             settle_o(Bk.o);
-            uint32_t worst = 0;
-            auto scan = [&](const Blk& X) {
-                worst |= (uint32_t)((__float_as_uint(X.l[0]) & 0x7f800000u) >= OUTGROWN_EXP);
-                worst |= (uint32_t)((__float_as_uint(X.l[1]) & 0x7f800000u) >= OUTGROWN_EXP);
-#pragma unroll
-                for (int d = 0; d < ND; ++d)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) worst |= (uint32_t)((__float_as_uint(X.o[d][e]) & 0x7f800000u) >= OUTGROWN_EXP);
-            };
-            scan(A);
-            scan(Bk);
-            outgrown = __any(worst != 0);
+            outgrown = __any(attn_out_of_range<false>(attn_out_of_range<false>(0u, A.l, A.o, L.lane), Bk.l, Bk.o, L.lane) != 0);
         }
-        if (outgrown && L.lane == 0) *redo_flag = 1;
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const int redo = *redo_flag;
-        __builtin_amdgcn_s_barrier();
+        const int redo = attn_agree_redo(redo_flag, outgrown, L.lane);
         if (attempt == 1 || redo == 0) break;
     }
 
 
-    // ---- epilogue: O = O^T / l, through a per-wave LDS scratch so that rows leave whole (attention.hip): 32 rows of 256 B,
-    // 16-byte chunks XOR-swizzled by the row
+    // ---- epilogue: O = O^T / l, through a per-wave LDS scratch so that rows leave whole: 32 rows of 256 B, 16-byte chunks
+    // XOR-swizzled by the row.  Not a helper shared with the other kernels: with this body moved into force-inlined functions
+    // this kernel came out with 253 instead of 255 VGPRs and 18 more spilled SGPRs.
     auto store = [&](Blk& X, int blk) {
         settle_o(X.o);
         const float l0 = __shfl(X.l[0], L.r & 15, 64), l1 = __shfl(X.l[1], L.r & 15, 64);
@@ -471,7 +390,7 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
         if (p.lse != nullptr) {
             // (wave-uniform) both forms take P against the row's reference X.m (raw scores): running maximum or fixed
             const int row = qt * Q_PER_WG + wave * 64 + 32 * blk + L.r;
-            if (L.hh == 0 && row < p.Lq) p.store_lse(b, head, row, X.m * c, lrow, false);
+            if (L.hh == 0 && row < p.Lq) p.store_lse(item.b, item.head, row, X.m * c, lrow, false);
         }
         char* scr = smem + (wave * 2 + blk) * (32 * ROW_BYTES);
 #pragma unroll
@@ -489,7 +408,7 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
         for (int t = 0; t < 8; ++t) {
             const int row = t * 4 + (L.lane >> 4), chunk = L.lane & 15;
             const u32x4 w = *(const u32x4*)(scr + row * ROW_BYTES + ((chunk ^ (row & 15)) << 4));
-            if (q0 + row < p.Lq) *(u32x4*)(ob + p.o_row(q0 + row) + chunk * 8) = w;
+            if (q0 + row < p.Lq) *(u32x4*)(item.o + p.o_row(q0 + row) + chunk * 8) = w;
         }
     };
     store(A, 0);
@@ -499,13 +418,8 @@ __global__ __launch_bounds__(256, 1) void attn_pipe128_kernel(AttnParams p) {
 }  // namespace pipe128
 
 int launch_attn_pipe128(AttnParams p, hipStream_t stream) {
-    auto kern = pipe128::attn_pipe128_kernel;
     static unsigned long long lds_done = 0;
-    if (const int rc = reserve_lds((const void*)kern, pipe128::SMEM + 16, &lds_done, "ltxmi_attention_fwd_bf16")) return rc;
-    p.q_tiles = (p.Lq + pipe128::Q_PER_WG - 1) / pipe128::Q_PER_WG;
-    const int64_t grid = (int64_t)p.B * p.H * p.q_tiles;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), pipe128::SMEM + 16, stream, p);
-    return check_launch("ltxmi_attention_fwd_bf16");
+    return attn_launch(pipe128::attn_pipe128_kernel, pipe128::SMEM + 16, &lds_done, p, (p.Lq + pipe128::Q_PER_WG - 1) / pipe128::Q_PER_WG, stream);
 }
 
 }  // namespace ltxmi

@@ -68,6 +68,14 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ---- XCD-aware work id: blocks b and b + 8 share an XCD (round-robin dispatch); give each XCD a contiguous run of
+// work ids, so that the CUs behind one L2 work on neighbours (bijective for any grid size)
+__device__ __forceinline__ int xcd_work_id() {
+    const int nwg = gridDim.x, orig = blockIdx.x;
+    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+
 // ---- async global -> LDS, 16 B per lane; LDS destination = wave-uniform base + lane*16
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((glb_void_ptr)gsrc, (lds_void_ptr)lds_wave_base, 16, 0, 0);

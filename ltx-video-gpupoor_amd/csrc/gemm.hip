@@ -106,13 +106,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(Gem
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-    // ---- XCD-aware tile id: blocks b and b+8 share an XCD (round-robin dispatch); give
-    // each XCD a contiguous run of tile ids (bijective form for any grid size).
-    const int nwg = gridDim.x;
-    const int orig = blockIdx.x;
-    const int xcd = orig & 7;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    // ---- XCD-aware tile id: each XCD gets a contiguous run of tile ids
+    const int tile = xcd_work_id();
     // tiles are numbered in bands of GN N-tiles, M-major inside a band: the ~32 tiles an XCD
     // runs concurrently form a (few M) x (GN N) patch that shares A rows AND W rows in L2
     constexpr int GN = 8;

@@ -1316,15 +1316,23 @@ def test_attention_q_norm_and_rope_on_load(B, H, N, per_sample_tables):
     check(fused[:, sel], truth, what="q finished on load vs oracle")
 
 
+# (the parameter tuples of test_attention_q_norm_on_load_generic_kernel that must run one particular kernel id)
+Q_ON_LOAD_KERNEL_ID = {(1, 128, 128, 256, 1024, False, True): 6}
+
+
 @pytest.mark.parametrize("B,H,dh,Lq,Lk,bias,rope", [(3, 32, 64, 4992, 256, True, False),     # the DiT's cross-attention
                                                     (2, 4, 64, 300, 77, True, False), (1, 2, 64, 100, 100, False, True),
-                                                    (1, 12, 128, 520, 520, False, True), (2, 3, 128, 130, 64, True, False)])
+                                                    (1, 12, 128, 520, 520, False, True), (2, 3, 128, 130, 64, True, False),
+                                                    (1, 128, 128, 256, 1024, False, True)])         # the pipelined head_dim-128 kernel
 def test_attention_q_norm_on_load_generic_kernel(B, H, dh, Lq, Lk, bias, rope):
     """The same fusion in the kernel that takes everything else (key bias, small shapes, head_dim 128 incl. its
-    scale-folded form): against the two-pass form."""
+    scale-folded form), and in the pipelined head_dim-128 kernel (id 6): against the two-pass form."""
     from ltxmi import ops
     D = H * dh
     assert ops.attention_fuses_qnorm(B, H, Lq, Lk, dh, bias)
+    want_id = Q_ON_LOAD_KERNEL_ID.get((B, H, dh, Lq, Lk, bias, rope))
+    if want_id is not None:
+        assert ops.attention_kernel_id(B, H, Lq, Lk, dh, bias, D, D) == want_id
     g = torch.Generator(device=DEV).manual_seed(171)
     q = (torch.randn(B * Lq, D, generator=g, device=DEV) * 1.7).to(BF)
     k = torch.randn(B, Lk, H, dh, generator=g, device=DEV).to(BF)
@@ -1340,8 +1348,19 @@ def test_attention_q_norm_on_load_generic_kernel(B, H, dh, Lq, Lk, bias, rope):
         cos = ang.cos().repeat_interleave(2, dim=-1).to(BF)
         sin = ang.sin().repeat_interleave(2, dim=-1).to(BF)
     ss = q.float().reshape(B * Lq, D // 64, 64).pow(2).sum(-1).contiguous()
-    ref = q.clone()
-    ops.rmsnorm_rope_(ref, wq, 1e-6, cos, sin, Lq if rope else 0)
+    if D <= 8192:
+        ref = q.clone()
+        ops.rmsnorm_rope_(ref, wq, 1e-6, cos, sin, Lq if rope else 0)
+    else:
+        # rows wider than the row kernel takes (only the D = 16384 case, 128 heads of 128, comes here): the first pass in
+        # torch, with that kernel's arithmetic -- fp32 x * rstd * weight, interleaved-pair rotation, ONE rounding to bf16
+        x = q.float()
+        o = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-6) * wq.float()
+        if rope:
+            c, s_ = cos.float().repeat(B, 1), sin.float().repeat(B, 1)
+            ev, od = o[:, 0::2], o[:, 1::2]
+            o = torch.stack((ev * c[:, 0::2] - od * s_[:, 0::2], od * c[:, 1::2] + ev * s_[:, 1::2]), dim=-1).reshape(B * Lq, D)
+        ref = o.to(BF)
     two_pass = ops.attention(ref.view(B, Lq, H, dh), k, v, key_bias=kb)
     fused = ops.attention(q.view(B, Lq, H, dh), k, v, key_bias=kb, q_norm=(ss, wq, 1e-6),
                           rope=(cos, sin, Lq) if rope else None)

@@ -26,7 +26,7 @@ def _usage(source, tmp_path):
         if m:
             name = m.group(1)
             usage[name] = {}
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
         if m and name:
             usage[name][m.group(1)] = int(m.group(2))
     return usage
@@ -47,3 +47,25 @@ def test_short_key_attention_kernel_does_not_spill(tmp_path):
     assert len(kernels) == 4, list(usage)
     for name, u in kernels.items():
         assert u["VGPRs Spill"] == 0 and u["ScratchSize [bytes/lane]"] == 0 and u["Occupancy [waves/SIMD]"] >= 2, (name, u)
+
+
+def test_pipelined_head_dim_128_kernel_keeps_its_register_split(tmp_path):
+    usage = _usage("attention_pipe128.hip", tmp_path)
+    kernels = {k: v for k, v in usage.items() if "attn_pipe128_kernel" in k}
+    assert len(kernels) == 1, list(usage)
+    for name, u in kernels.items():
+        assert u["VGPRs Spill"] == 0 and u["ScratchSize [bytes/lane]"] == 0 and u["Occupancy [waves/SIMD]"] == 1, (name, u)
+        assert u["AGPRs"] > 0, (name, u)                        # the hand-pinned accumulator split is in force
+
+
+def test_generic_attention_kernel_does_not_spill(tmp_path):
+    usage = _usage("attention.hip", tmp_path)
+    # <head_dim, key bias, 32-row query blocks per wave> -> occupancy floor (waves per SIMD) per instance
+    floor = {"Li64ELb0ELi1E": 3, "Li64ELb1ELi1E": 3, "Li64ELb0ELi2E": 2, "Li128ELb0ELi1E": 2, "Li128ELb1ELi1E": 2}
+    kernels = {k: v for k, v in usage.items() if "attn_fwd_kernel" in k}
+    assert len(kernels) == 5, list(usage)
+    for name, u in kernels.items():
+        inst = [f for f in floor if "attn_fwd_kernelI" + f in name]
+        assert len(inst) == 1, name
+        assert u["VGPRs Spill"] == 0 and u["ScratchSize [bytes/lane]"] == 0, (name, u)
+        assert u["Occupancy [waves/SIMD]"] >= floor[inst[0]], (name, u)
