@@ -21,7 +21,7 @@
  *     set (`ltxmi_gemm_args a = {0};` / memset): versions append optional fields at the tail
  *     (0.2: rowsumsq*, a_kblock* of ltxmi_gemm_args; q_rowsumsq*, q_norm*, rope_*, o_segment*
  *     of ltxmi_attn_args; 0.3: q_rstd*; 0.4: conv3d post_*; 0.5: redo_counter, force_exact of ltxmi_attn_args, y_norm, workspace of ltxmi_conv3d_args;
- *     0.6: lse* of ltxmi_attn_args; 0.7: no field -- ltxmi_gemm_kernel_id, ltxmi_gemm_args.algo = 256 is honoured for every
+ *     0.6: lse* of ltxmi_attn_args; 0.7: no field -- ltxmi_gemm_kernel_id, ltxmi_conv3d_route, ltxmi_gemm_args.algo = 256 is honoured for every
  *     shape, and the GEMM entry check refuses a bad epilogue and a residual / gate pointer off an 8-byte boundary),
  *     and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
@@ -314,7 +314,8 @@ typedef struct ltxmi_conv3d_args {
     const void* residual;      /* d2s only: x itself (pre-conv block input) or NULL       */
     int32_t res_channels;      /* channels of the residual tensor (Cin of the block)      */
     const void* add;           /* plain store only: y = conv + add, add [B,T,H,W,Cout] or NULL
-                                  (ResnetBlock3D skip, causal_video_autoencoder.py:1256)   */
+                                  (ResnetBlock3D skip, causal_video_autoencoder.py:1256); added in fp32, before the ONE
+                                  rounding to bf16, on every route                          */
     /* encoder-side extensions (0 = default): strided causal convolutions of the "compress_*"
      * encoder blocks (causal_video_autoencoder.py:395-432) and the extended-in-time convolution of
      * SpaceToDepthDownsample, which runs on the input with its first frame duplicated (:991-1009):
@@ -369,6 +370,25 @@ int ltxmi_conv3d_fuses_post_norm(const ltxmi_conv3d_args* args);
  * ltxmi_conv3d_args.workspace); 0 when it would not.  Reads the shape, flags, algo and post_norm (at 512 input channels the split
  * pays only when the finalising pass takes a norm along); ignores args->workspace*. */
 int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* args);
+/* 0.7 -- how ltxmi_conv3d_ndhwc_bf16 would run these arguments.  It is the launch's own check and plan, host arithmetic only:
+ * nothing is launched, no device is needed and no pointer is dereferenced -- it reads the shape, flags, algo, post_norm and the
+ * fields the entry check validates, the ADDRESSES of x, w, y, bias, post_scale / post_shift and y_norm (NULL-ness, alignment),
+ * and workspace / workspace_bytes exactly as the launch does (a workspace that is missing, misaligned or smaller than
+ * ltxmi_conv3d_workspace_bytes() means the unsplit route).  Returns the status the launch would return (0, or the negative
+ * ltxmi_status with ltxmi_last_error() saying why; *out then holds route = -1 and zeros).  0.7 also moves the refusal of `add`
+ * together with d2s (LTXMI_ERR_INVALID_ARG) from the implicit GEMM's launcher into that check. */
+typedef struct ltxmi_conv3d_route_info {
+    int32_t route;            /* 0 implicit GEMM, 128 x 128 tiles; 1 implicit GEMM, 256 x 256 tiles; 2 direct convolution,
+                                 eight waves per workgroup; 3 direct convolution, four waves per workgroup                    */
+    int32_t epilogue;         /* the epilogue the convolution kernel is launched with: 0 plain store, 1 + add, 2 depth-to-space
+                                 (every route); the four-wave direct form also 3 / 4 / 5 = 0 / 1 / 2 with post_norm applied
+                                 (4, 5: to y_norm), and 6 = fp32 partial sums of a channel split into the workspace           */
+    int32_t ksplit;           /* ranges the input channels are split into: 1 (no split), or 2 .. 4 with epilogue 6             */
+    int32_t swap_hw;          /* four-wave direct form: 1 = the 16-position rows of its 2 x 8 x 16 tiles run along H, 0 along W */
+    int32_t finalize_blocks;  /* ksplit > 1: Cout / 256, which picks the finalising pass's instantiation (2, 4, 8, 12 or 16:
+                                 the pass holds whole rows and applies bias, add / depth-to-space + residual, post_norm); else 0 */
+} ltxmi_conv3d_route_info;
+int ltxmi_conv3d_route(const ltxmi_conv3d_args* args, ltxmi_conv3d_route_info* out);
 
 /* PixelNorm (pixel_norm.py:5-12, eps 1e-8) -> optional (1+scale)*x+shift per (batch, channel)
  * (ResnetBlock3D AdaLN, causal_video_autoencoder.py:1206-1243, Decoder tail :771-795)

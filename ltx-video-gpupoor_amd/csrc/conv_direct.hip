@@ -399,20 +399,21 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     u32x2 bias_v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) bias_v[j] = *(const u32x2*)(p.bias + min(n0 + wn * 64 + j * 16 + ecol, p.Cout - 4));
-    // y = conv + add: the eight 16-byte pieces of `add` this lane needs are requested up front, from clamped (always valid)
-    // addresses -- loaded where they are used, each sat behind a branch and an s_waitcnt vmcnt(0) that also waited for the
-    // store before it: eight serialised memory round trips per tile, ~7 % of a 128-channel layer's time
-    u32x4 add_v[2][4];
+    // y = conv + add, added in fp32 BEFORE the one rounding to bf16 (as the implicit GEMM does: adding to the rounded value rounds
+    // twice, and where conv and add cancel the first rounding's error is all that is left).  The sixteen 8-byte pieces of `add`
+    // this lane needs, in the accumulators' layout, are requested up front from clamped (always valid) addresses: loaded where
+    // they are used, each would sit behind a branch and an s_waitcnt vmcnt(0) -- serialised memory round trips, ~7 % of a
+    // 128-channel layer's time
+    u32x2 add_f[4][4];
     if (ADD) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
+        for (int i = 0; i < 4; ++i) {
+            const int pos = wm * 64 + i * 16 + frow;
+            const int t = min(t0 + (pos >> 7), p.T - 1), yy = min(y0 + ((pos >> 4) & 7), p.H - 1), xx = min(x0 + (pos & 15), p.W - 1);
+            const uint16_t* arow = p.add + ((((int64_t)b * p.T + t) * p.H + yy) * p.W + xx) * p.Cout;
 #pragma unroll
-            for (int t4 = 0; t4 < 4; ++t4) {
-                const int pos = wm * 64 + c * 32 + t4 * 8 + (lane >> 3);
-                const int t = min(t0 + (pos >> 7), p.T - 1), yy = min(y0 + ((pos >> 4) & 7), p.H - 1), xx = min(x0 + (pos & 15), p.W - 1);
-                const int n = min(n0 + wn * 64 + (lane & 7) * 8, p.Cout - 8);
-                add_v[c][t4] = *(const u32x4*)(p.add + ((((int64_t)b * p.T + t) * p.H + yy) * p.W + xx) * p.Cout + n);
-            }
+            for (int j = 0; j < 4; ++j) add_f[i][j] = *(const u32x2*)(arow + min(n0 + wn * 64 + j * 16 + ecol, p.Cout - 4));
+        }
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -435,6 +436,12 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
                     const int cm = p.res_ch >> 3;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] += bf2f(rrow[((cp + e) % cm) * 8]);
+                }
+                if (ADD) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(v[e]));      // (conv + bias) + add, in this order
+                    v[0] += bf_lo(add_f[i][j][0]); v[1] += bf_hi(add_f[i][j][0]);
+                    v[2] += bf_lo(add_f[i][j][1]); v[3] += bf_hi(add_f[i][j][1]);
                 }
                 u32x2 o;
                 o[0] = pack_bf16(v[0], v[1]);
@@ -459,12 +466,6 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
                 }
             } else if (t < p.T && yy < p.H && xx < p.W && n0 + wn * 64 + chunk * 8 < p.Cout) {
                 const int64_t off = ((((int64_t)b * p.T + t) * p.H + yy) * p.W + xx) * p.Cout + n0 + wn * 64 + chunk * 8;
-                if (ADD) {
-                    const u32x4 r = add_v[c][t4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        w[e] = pack_bf16(bf_lo(w[e]) + bf_lo(r[e]), bf_hi(w[e]) + bf_hi(r[e]));
-                }
                 *(u32x4*)(p.y + off) = w;
             }
         }
@@ -766,26 +767,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
         const int t = min(t0 + (pos >> 7), p.T - 1), yy = min(img_y((pos >> 4) & 7, pos & 15), p.H - 1), xx = min(img_x((pos >> 4) & 7, pos & 15), p.W - 1);
         prow[i] = (((int64_t)b * p.T + t) * p.H + yy) * p.W + xx;
     }
-    u32x4 add_v[2][2][4];                                                  // EPI 1: `add` in the stores' row-major layout
-    if (ADD && !DUAL) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int t4 = 0; t4 < 4; ++t4) {
-                    const int pos = wave * 64 + c * 32 + t4 * 8 + (lane >> 3);
-                    const int t = min(t0 + (pos >> 7), p.T - 1), yy = min(img_y((pos >> 4) & 7, pos & 15), p.H - 1), xx = min(img_x((pos >> 4) & 7, pos & 15), p.W - 1);
-                    const int n = min(n0 + h * 64 + (lane & 7) * 8, p.Cout - 8);
-                    add_v[h][c][t4] = *(const u32x4*)(p.add + ((((int64_t)b * p.T + t) * p.H + yy) * p.W + xx) * p.Cout + n);
-                }
-    }
-    u32x2 add_f[4][8];                                                     // EPI 4: `add` in the accumulators' layout
-    if (ADD && DUAL) {
+    u32x2 add_f[4][8];                                                     // EPI 1 / 4: `add` in the accumulators' layout
+    if (ADD) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) add_f[i][j] = *(const u32x2*)(p.add + prow[i] * 128 + j * 16 + ecol);
+            for (int j = 0; j < 8; ++j) add_f[i][j] = *(const u32x2*)(p.add + prow[i] * p.Cout + n0 + j * 16 + ecol);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -795,6 +782,18 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
             acc[i][j][0] += bf_lo(bv[0]); acc[i][j][1] += bf_hi(bv[0]);
             acc[i][j][2] += bf_lo(bv[1]); acc[i][j][3] += bf_hi(bv[1]);
         }
+    }
+    if (ADD) {
+        // y = (conv + bias) + add in fp32, in this order, BEFORE the one rounding to bf16 (as the implicit GEMM does)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                asm volatile("" : "+v"(acc[i][j]));
+                const u32x2 a2 = add_f[i][j];
+                acc[i][j][0] += bf_lo(a2[0]); acc[i][j][1] += bf_hi(a2[0]);
+                acc[i][j][2] += bf_lo(a2[1]); acc[i][j][3] += bf_hi(a2[1]);
+            }
     }
     if (D2S && p.res) {
         // x_in = repeat(pixel_shuffle(x)): channel c' <- x[(c' mod (Cres/8)) * 8 + pp]   (gemm.hip, EPI_D2S); (conv + bias) + x_in
@@ -819,18 +818,13 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
         }
     }
     if (DUAL) {
-        // y exactly as EPI 1 / 2 store it, kept in the accumulators as bf16-representable floats: bf16(conv + bias) then + add in
-        // bf16 (EPI 1 rounds twice), or bf16(conv + bias + residual) (EPI 2 rounds once)
+        // y exactly as EPI 1 / 2 store it, kept in the accumulators as bf16-representable floats: bf16(conv + bias + add), or
+        // bf16(conv + bias + residual) -- one rounding
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                uint32_t r0 = pack_bf16(acc[i][j][0], acc[i][j][1]), r1 = pack_bf16(acc[i][j][2], acc[i][j][3]);
-                if (ADD) {
-                    const u32x2 a2 = add_f[i][j];
-                    r0 = pack_bf16(bf_lo(r0) + bf_lo(a2[0]), bf_hi(r0) + bf_hi(a2[0]));
-                    r1 = pack_bf16(bf_lo(r1) + bf_lo(a2[1]), bf_hi(r1) + bf_hi(a2[1]));
-                }
+                const uint32_t r0 = pack_bf16(acc[i][j][0], acc[i][j][1]), r1 = pack_bf16(acc[i][j][2], acc[i][j][3]);
                 acc[i][j][0] = bf_lo(r0); acc[i][j][1] = bf_hi(r0);
                 acc[i][j][2] = bf_lo(r1); acc[i][j][3] = bf_hi(r1);
             }
@@ -899,12 +893,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
                         }
                     } else if (t < p.T && yy < p.H && xx < p.W && n0 + h * 64 + chunk * 8 < p.Cout) {
                         const int64_t off = ((((int64_t)b * p.T + t) * p.H + yy) * p.W + xx) * p.Cout + n0 + h * 64 + chunk * 8;
-                        if (ADD && !DUAL) {
-                            const u32x4 r = add_v[h][c][t4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                w[e] = pack_bf16(bf_lo(w[e]) + bf_lo(r[e]), bf_hi(w[e]) + bf_hi(r[e]));
-                        }
                         *(u32x4*)(dst + off) = w;
                     }
                 }
@@ -922,8 +910,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
 // bias and applies the epilogue of the layer: plain store, + add, or the depth-to-space store (+ residual), each with the
 // optional PixelNorm -> (1 + scale) x + shift -> SiLU as the only or as a second output (a row of the partial sums holds every
 // channel of its position(s), so the norm rides here at any width).  The arithmetic of the values mirrors the fused epilogues:
-// y = bf16(sum + bias [+ residual]), `add` added to the rounded value and rounded again, the statistic from the bf16 values when
-// the raw result is kept and from the fp32 ones when only the activated result is (EPI 3's form).
+// y = bf16(sum + bias [+ residual | + add]) with ONE rounding, the statistic from the bf16 values when the raw result is kept and
+// from the fp32 ones when only the activated result is (EPI 3's form).
 struct ConvFinalizeP {
     const float* part; int ksplit; int64_t rows;             // [ksplit][rows][Cout]
     const uint16_t* bias; const uint16_t* add; const uint16_t* res; int res_ch;
@@ -974,15 +962,19 @@ __global__ __launch_bounds__(NT) void conv_split_finalize_kernel(ConvFinalizeP f
         }
     }
     const bool keep_raw = f.y != nullptr;
+    if (f.add) {
+#pragma unroll
+        for (int q = 0; q < CPT / 2; ++q) {
+            const uint32_t a = *(const uint32_t*)(f.add + row * f.Cout + c0 + 2 * q);
+            asm volatile("" : "+v"(v[2 * q]), "+v"(v[2 * q + 1]));       // (sum + bias) + add, in this order
+            v[2 * q] += bf_lo(a); v[2 * q + 1] += bf_hi(a);
+        }
+    }
     if (keep_raw) {
         // the raw result as the fused epilogues round it
 #pragma unroll
         for (int q = 0; q < CPT / 2; ++q) {
-            uint32_t r = pack_bf16(v[2 * q], v[2 * q + 1]);
-            if (f.add) {
-                const uint32_t a = *(const uint32_t*)(f.add + row * f.Cout + c0 + 2 * q);
-                r = pack_bf16(bf_lo(r) + bf_lo(a), bf_hi(r) + bf_hi(a));
-            }
+            const uint32_t r = pack_bf16(v[2 * q], v[2 * q + 1]);
             v[2 * q] = bf_lo(r); v[2 * q + 1] = bf_hi(r);
         }
     }
@@ -1240,11 +1232,14 @@ static bool conv3d_plannable(const ltxmi_conv3d_args* a) {
 extern "C" int ltxmi_conv3d_fuses_post_norm(const ltxmi_conv3d_args* a) { return conv3d_plannable(a) && conv3d_plan(a).fuses_post_norm; }
 extern "C" int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* a) { return conv3d_plannable(a) ? conv3d_plan(a).split_bytes : 0; }
 
-extern "C" int ltxmi_conv3d_ndhwc_bf16(const ltxmi_conv3d_args* a, void* stream) {
+// The ONE place that validates a convolution call and plans it: ltxmi_conv3d_ndhwc_bf16 launches what this leaves in *pl and
+// ltxmi_conv3d_route reports it.  Pure host arithmetic on the struct: no device call, no device memory read.  Returns LTXMI_OK
+// with the plan in *pl, or the negative ltxmi_status (error text set).
+static int conv3d_check(const ltxmi_conv3d_args* a, ConvPlan* plan) {
     LTXMI_REQUIRE(a && a->x && a->w && a->y, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: NULL argument");
     LTXMI_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_conv3d_ndhwc_bf16: non-positive shape");
-    const ConvPlan pl = conv3d_plan(a);
+    const ConvPlan pl = *plan = conv3d_plan(a);
     LTXMI_REQUIRE(a->Cin % 64 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cin=%d must be a multiple of 64", a->Cin);
     LTXMI_REQUIRE(a->Cout % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cout=%d must be a multiple of 8", a->Cout);
     LTXMI_REQUIRE((pl.sT == 1 || pl.sT == 2) && (pl.sHW == 1 || pl.sHW == 2), LTXMI_ERR_UNSUPPORTED,
@@ -1280,13 +1275,29 @@ extern "C" int ltxmi_conv3d_ndhwc_bf16(const ltxmi_conv3d_args* a, void* stream)
     } else {
         LTXMI_REQUIRE(a->y_norm == nullptr, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: y_norm without post_norm");
     }
-    switch (pl.route) {
-        case CONV_DIRECT4:
-        case CONV_DIRECT8: return launch_conv3d_direct(a, pl, (hipStream_t)stream);
-        case CONV_GEMM128:
-        case CONV_GEMM256: return launch_conv3d_gemm(a, pl, (hipStream_t)stream);
-        case CONV_REFUSED: break;
-    }
-    set_error("ltxmi_conv3d_ndhwc_bf16: algo = %d (direct convolution) does not take this shape", a->algo);
-    return LTXMI_ERR_UNSUPPORTED;
+    LTXMI_REQUIRE(pl.route != CONV_REFUSED, LTXMI_ERR_UNSUPPORTED,
+                  "ltxmi_conv3d_ndhwc_bf16: algo = %d (direct convolution) does not take this shape", a->algo);
+    // (`d2s` with `add` never reaches the direct forms: conv3d_direct_takes)
+    LTXMI_REQUIRE(!(a->d2s && a->add), LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: `add` is for the plain store only");
+    return LTXMI_OK;
+}
+
+extern "C" int ltxmi_conv3d_route(const ltxmi_conv3d_args* a, ltxmi_conv3d_route_info* out) {
+    LTXMI_REQUIRE(out != nullptr, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_route: NULL out");
+    *out = ltxmi_conv3d_route_info{-1, 0, 0, 0, 0};
+    ConvPlan pl;
+    if (const int rc = conv3d_check(a, &pl)) return rc;
+    out->route = (int32_t)pl.route;               // CONV_GEMM128 .. CONV_DIRECT4 are 0 .. 3, the header's numbering
+    out->epilogue = pl.epi;
+    out->ksplit = pl.ksplit;
+    out->swap_hw = pl.swap;
+    out->finalize_blocks = pl.ksplit > 1 ? a->Cout / 256 : 0;
+    return LTXMI_OK;
+}
+
+extern "C" int ltxmi_conv3d_ndhwc_bf16(const ltxmi_conv3d_args* a, void* stream) {
+    ConvPlan pl;
+    if (const int rc = conv3d_check(a, &pl)) return rc;
+    if (pl.route == CONV_DIRECT4 || pl.route == CONV_DIRECT8) return launch_conv3d_direct(a, pl, (hipStream_t)stream);
+    return launch_conv3d_gemm(a, pl, (hipStream_t)stream);
 }

@@ -969,7 +969,6 @@ int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream
     p.pad_replicate = a->pad_replicate;
     p.res = a->d2s ? (const uint16_t*)a->residual : nullptr;
     p.res_ch = a->res_channels;
-    LTXMI_REQUIRE(!(a->d2s && a->add), LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: `add` is for the plain store only");
     if (a->add) { p.R = (const uint16_t*)a->add; p.ldr = a->Cout; }
     const int epi = pl.epi == 2 ? EPI_D2S : (pl.epi == 1 ? EPI_RESIDUAL : LTXMI_EPI_NONE);
     if (pl.route == CONV_GEMM256) return launch_tile<256, 256, 2, 4, 1>(p, epi, stream, "ltxmi_conv3d_ndhwc_bf16");

@@ -70,6 +70,10 @@ class Conv3dArgs(ctypes.Structure):
                 ("y_norm", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
 
 
+class Conv3dRouteInfo(ctypes.Structure):
+    _fields_ = [("route", c_int), ("epilogue", c_int), ("ksplit", c_int), ("swap_hw", c_int), ("finalize_blocks", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/ltxmi.h one to one
 SIGNATURES = {
     "ltxmi_version": (ctypes.c_char_p, []),
@@ -98,6 +102,7 @@ SIGNATURES = {
     "ltxmi_conv3d_ndhwc_bf16": (c_int, [ctypes.POINTER(Conv3dArgs), c_void_p]),
     "ltxmi_conv3d_fuses_post_norm": (c_int, [ctypes.POINTER(Conv3dArgs)]),
     "ltxmi_conv3d_workspace_bytes": (c_int64, [ctypes.POINTER(Conv3dArgs)]),
+    "ltxmi_conv3d_route": (c_int, [ctypes.POINTER(Conv3dArgs), ctypes.POINTER(Conv3dRouteInfo)]),
     "ltxmi_pixelnorm_ada_silu_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p,
                                               c_int, c_float, c_void_p]),
     "ltxmi_add_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

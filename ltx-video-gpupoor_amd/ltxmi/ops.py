@@ -469,19 +469,12 @@ CONV_SPLIT = True
 _conv_workspace = {}
 
 
-def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, add=None, out=None,
-           stride=(1, 1, 1), tpad=0, out_T=0, kernel_t=3, time_pad_zeros=False, algo=None, post_norm=None, keep_raw=False):
-    """x [B,T,H,W,Cin] NDHWC; w_packed [Cout, 27*Cin] (tap-major; (p1p2p3, c')-major rows when d2s).
-    stride = (st, s, s) with st, s in {1, 2}; tpad / out_T: front time padding and output frames
-    when they differ from CausalConv3d's (0 = default); kernel_t = 1: per-frame 3x3 Conv2d
-    (w_packed [Cout, 9*Cin]); time_pad_zeros: nn.Conv3d zero padding in time.  See include/ltxmi.h.
-    post_norm = (scale fp32 [B,Cout] or None, shift, eps): the result goes through PixelNorm -> (1+scale) x + shift -> SiLU
-    (``pixelnorm_ada_silu``) -- in the convolution's epilogue where the kernel can (ltxmi_conv3d_fuses_post_norm), as a
-    second launch on the result otherwise.
-    keep_raw (with post_norm): return (raw, activated) -- the raw result too, for the skip path of the block that consumes the
-    activated one (the NEXT block's norm1 -> AdaLN -> SiLU riding on this convolution: ltxmi_conv3d_args.y_norm); allowed
-    with `add` and with d2s."""
-    _chk_bf16(x, w_packed, bias, residual, add, out)
+def _conv3d_args(x, w_packed, bias, causal, pad_replicate, d2s, residual, add, out, stride, tpad, out_T, kernel_t,
+                 time_pad_zeros, algo, post_norm, keep_raw, workspace, out_norm, launch):
+    """The ltxmi_conv3d_args of a ``conv3d`` / ``conv3d_route`` call -> (args, out, out_norm, second_launch, key).  ``launch``
+    False (the route query): nothing is allocated -- a missing ``out`` / second output / workspace is stood in for by what a
+    fresh allocation always is, 16-byte aligned and large enough -- and the tensors may live on any device."""
+    (_chk_bf16 if launch else _chk_bf16_any_device)(x, w_packed, bias, residual, add, out, out_norm)
     B, T, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
     if not x.is_contiguous() or not w_packed.is_contiguous():
@@ -497,13 +490,12 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
     if w_packed.shape[1] != 9 * kernel_t * Cin:
         raise ValueError(f"ltxmi.conv3d: packed weight has K={w_packed.shape[1]}, expected {9 * kernel_t * Cin}")
     oH, oW = (H - 1) // sh + 1, (W - 1) // sh + 1
-    if out is None:
-        if d2s:
-            out = torch.empty((B, 2 * T - 1, 2 * H, 2 * W, Cout // 8), dtype=BF16, device=x.device)
-        else:
-            out = torch.empty((B, oT, oH, oW, Cout), dtype=BF16, device=x.device)
+    out_shape = (B, 2 * T - 1, 2 * H, 2 * W, Cout // 8) if d2s else (B, oT, oH, oW, Cout)
+    if out is None and launch:
+        out = torch.empty(out_shape, dtype=BF16, device=x.device)
     a = _lib.Conv3dArgs()
-    a.x, a.w, a.bias, a.y = x.data_ptr(), w_packed.data_ptr(), (bias.data_ptr() if bias is not None else None), out.data_ptr()
+    a.x, a.w, a.bias = x.data_ptr(), w_packed.data_ptr(), (bias.data_ptr() if bias is not None else None)
+    a.y = out.data_ptr() if out is not None else 256
     a.B, a.T, a.H, a.W, a.Cin, a.Cout = B, T, H, W, Cin, Cout
     a.causal, a.pad_replicate, a.d2s = int(causal), int(pad_replicate), int(d2s)
     a.stride_t, a.stride_hw, a.tpad, a.out_T = st, sh, tpad, out_T
@@ -515,7 +507,8 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
         if not add.is_contiguous() or add.shape != (B, oT, oH, oW, Cout):
             raise ValueError("ltxmi.conv3d: `add` must be a contiguous [B,T,H,W,Cout] tensor")
         a.add = add.data_ptr()
-    out_norm = None
+    if out_norm is not None and (not keep_raw or not out_norm.is_contiguous() or out_norm.shape != out_shape):
+        raise ValueError("ltxmi.conv3d: out_norm is the second output of keep_raw, contiguous and of the output's shape")
     if keep_raw and post_norm is None:
         raise ValueError("ltxmi.conv3d: keep_raw is for post_norm")
     if post_norm is not None:
@@ -525,20 +518,28 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
                              "without `add`")
         c_norm = Cout // 8 if d2s else Cout
         for t in (scale, shift):
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, c_norm) or not t.is_cuda):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != (B, c_norm)
+                                  or (launch and not t.is_cuda)):
                 raise ValueError("ltxmi.conv3d: post_norm scale / shift must be contiguous fp32 [B, C] device tensors")
-        if keep_raw:
-            out_norm = torch.empty_like(out)
+        if keep_raw and launch and out_norm is None:
+            out_norm = torch.empty(out_shape, dtype=BF16, device=x.device)
         if CONV_SECOND_OUTPUT_FUSE if keep_raw else CONV_POST_NORM_FUSE:
             a.post_norm, a.post_scale, a.post_shift, a.post_eps = 1, _ptr(scale), _ptr(shift), eps
             if keep_raw:
-                a.y_norm = out_norm.data_ptr()
+                a.y_norm = out_norm.data_ptr() if out_norm is not None else 512
     # Scratch for the channel-split form of the wide, short layers (ltxmi_conv3d_args.workspace): one buffer per (device, stream),
     # grown on demand, shared by every call on that stream (stream-ordered: the next call's writes follow this call's reads).  Asked
     # with the norm request in place (at 512 input channels the split pays only when the norm rides along), as the launch sees it.
-    if CONV_SPLIT:
+    # ``workspace`` (a uint8 tensor): the caller's own scratch instead, handed to the library as it is, whatever its size.
+    if workspace is not None:
+        if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or (launch and not workspace.is_cuda):
+            raise ValueError("ltxmi.conv3d: workspace must be a contiguous uint8 device tensor")
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    elif CONV_SPLIT:
         want = int(lib.ltxmi_conv3d_workspace_bytes(ctypes.byref(a)))
-        if want > 0:
+        if want > 0 and not launch:
+            a.workspace, a.workspace_bytes = 256, want
+        elif want > 0:
             key = (x.device, torch.cuda.current_stream().cuda_stream)
             ws = _conv_workspace.get(key)
             if ws is None or ws.numel() < want:
@@ -551,12 +552,57 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
     second_launch = post_norm if post_norm is not None and not a.post_norm else None
     # (watched either by shape alone or by shape + epilogue: "plain" / "add" / "post_norm" / "second_output")
     kind = ("second_output" if a.y_norm else "post_norm") if a.post_norm else ("add" if add is not None else "plain")
-    tok = _prof_begin(("conv3d", B * oT * oH * oW, Cin, Cout, int(d2s)), ("conv3d", B * oT * oH * oW, Cin, Cout, int(d2s), kind))
+    key = ("conv3d", B * oT * oH * oW, Cin, Cout, int(d2s))
+    return a, out, out_norm, second_launch, (key, key + (kind,))
+
+
+def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, add=None, out=None,
+           stride=(1, 1, 1), tpad=0, out_T=0, kernel_t=3, time_pad_zeros=False, algo=None, post_norm=None, keep_raw=False,
+           workspace=None, out_norm=None):
+    """x [B,T,H,W,Cin] NDHWC; w_packed [Cout, 27*Cin] (tap-major; (p1p2p3, c')-major rows when d2s).
+    stride = (st, s, s) with st, s in {1, 2}; tpad / out_T: front time padding and output frames
+    when they differ from CausalConv3d's (0 = default); kernel_t = 1: per-frame 3x3 Conv2d
+    (w_packed [Cout, 9*Cin]); time_pad_zeros: nn.Conv3d zero padding in time.  See include/ltxmi.h.
+    post_norm = (scale fp32 [B,Cout] or None, shift, eps): the result goes through PixelNorm -> (1+scale) x + shift -> SiLU
+    (``pixelnorm_ada_silu``) -- in the convolution's epilogue where the kernel can (ltxmi_conv3d_fuses_post_norm), as a
+    second launch on the result otherwise.
+    keep_raw (with post_norm): return (raw, activated) -- the raw result too, for the skip path of the block that consumes the
+    activated one (the NEXT block's norm1 -> AdaLN -> SiLU riding on this convolution: ltxmi_conv3d_args.y_norm); allowed
+    with `add` and with d2s.
+    workspace: a uint8 device tensor to use as ltxmi_conv3d_args.workspace instead of the module's own buffer; out_norm: where
+    keep_raw's activated output goes (allocated if None)."""
+    a, out, out_norm, second_launch, keys = _conv3d_args(x, w_packed, bias, causal, pad_replicate, d2s, residual, add, out, stride,
+                                                         tpad, out_T, kernel_t, time_pad_zeros, algo, post_norm, keep_raw,
+                                                         workspace, out_norm, True)
+    tok = _prof_begin(*keys)
     check(lib.ltxmi_conv3d_ndhwc_bf16(ctypes.byref(a), _stream()), "ltxmi_conv3d_ndhwc_bf16")
     _prof_end(tok)
     if second_launch is not None:
         pixelnorm_ada_silu(out, second_launch[0], second_launch[1], True, second_launch[2], out=out_norm if keep_raw else out)
     return (out, out_norm) if keep_raw else out
+
+
+# include/ltxmi.h: ltxmi_conv3d_route_info.route
+CONV_GEMM128, CONV_GEMM256, CONV_DIRECT8, CONV_DIRECT4 = 0, 1, 2, 3
+
+
+def conv3d_route(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, add=None, out=None,
+                 stride=(1, 1, 1), tpad=0, out_T=0, kernel_t=3, time_pad_zeros=False, algo=None, post_norm=None, keep_raw=False,
+                 workspace=None, out_norm=None):
+    """How ``conv3d`` runs the same arguments: dict(route, epilogue, ksplit, swap_hw, finalize_blocks, second_launch) of
+    ltxmi_conv3d_route_info (include/ltxmi.h) for the convolution launch ``conv3d`` makes -- ``second_launch``: the norm
+    follows as a launch of its own -- or the negative status ``conv3d`` would raise on.  Built from the same struct as the launch
+    and decided by the same code; nothing is launched or read, so the tensors may live on any device (only their shapes and
+    addresses count)."""
+    a, _, _, second_launch, _ = _conv3d_args(x, w_packed, bias, causal, pad_replicate, d2s, residual, add, out, stride, tpad,
+                                             out_T, kernel_t, time_pad_zeros, algo, post_norm, keep_raw, workspace, out_norm,
+                                             False)
+    info = _lib.Conv3dRouteInfo()
+    rc = int(lib.ltxmi_conv3d_route(ctypes.byref(a), ctypes.byref(info)))
+    if rc != 0:
+        return rc
+    return dict(route=info.route, epilogue=info.epilogue, ksplit=info.ksplit, swap_hw=info.swap_hw,
+                finalize_blocks=info.finalize_blocks, second_launch=second_launch is not None)
 
 
 def pixelnorm_ada_silu(x, scale=None, shift=None, apply_silu=True, eps=1e-8, out=None):

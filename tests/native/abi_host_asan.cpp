@@ -238,7 +238,17 @@ int main() {
     c.workspace = pf; c.workspace_bytes = want;
     if (ltxmi_conv3d_fuses_post_norm(&c) != 1) { fprintf(stderr, "FAIL fuses_post_norm(Cout 1024, workspace)\n"); ++g_bad; }
     expect_fail(ltxmi_conv3d_ndhwc_bf16(&c, nullptr), "conv3d(split + post_norm, no device)");
+    // ltxmi_conv3d_route (0.7): the launch's own check and plan -- three ranges on tiles with their rows along H, then the
+    // finalising pass for 1024 / 256 = 4 channel blocks; the statuses of the launch for what it refuses
+    ltxmi_conv3d_route_info ri;
+    if (ltxmi_conv3d_route(&c, &ri) != LTXMI_OK || ri.route != 3 || ri.epilogue != 6 || ri.ksplit != 3 || ri.swap_hw != 1 || ri.finalize_blocks != 4) {
+        fprintf(stderr, "FAIL conv3d_route(split + post_norm) = %d %d %d %d %d\n", ri.route, ri.epilogue, ri.ksplit, ri.swap_hw, ri.finalize_blocks); ++g_bad;
+    }
+    expect_fail(ltxmi_conv3d_route(&c, nullptr), "conv3d_route(NULL out)", LTXMI_ERR_INVALID_ARG);
+    expect_fail(ltxmi_conv3d_route(nullptr, &ri), "conv3d_route(NULL args)", LTXMI_ERR_INVALID_ARG);
     c.workspace_bytes = want - 4;
+    expect_fail(ltxmi_conv3d_route(&c, &ri), "conv3d_route(post_norm, workspace too small)", LTXMI_ERR_UNSUPPORTED);
+    if (ri.route != -1 || ri.ksplit != 0) { fprintf(stderr, "FAIL conv3d_route leaves route -1 on a refusal\n"); ++g_bad; }
     if (ltxmi_conv3d_fuses_post_norm(&c) != 0) { fprintf(stderr, "FAIL fuses_post_norm(workspace too small)\n"); ++g_bad; }
     c.workspace = nullptr; c.workspace_bytes = want;
     expect_fail(ltxmi_conv3d_ndhwc_bf16(&c, nullptr), "conv3d(workspace_bytes without a workspace)", LTXMI_ERR_INVALID_ARG);

@@ -280,6 +280,101 @@ def test_gemm_kernel_id_through_ops_needs_no_device():
         ops.gemm_kernel_id(a.float(), w)
 
 
+# ltxmi_conv3d_route: (what, overrides of the struct built by _conv_geometry, status or (route, epilogue, ksplit, swap_hw,
+# finalize_blocks)).  Routes: 0 / 1 the implicit GEMM with 128 / 256 tiles, 2 / 3 the eight- / four-wave direct convolution.
+# Worked out by hand from include/ltxmi.h and conv3d_plan's comments (direct tiles are 2 x 8 x 16 positions x 128 channels).
+CONV_ROUTES = [
+    ("24576 x 256: 192 direct tiles -> eight waves", {}, (2, 0, 1, 0, 0)),
+    ("... + add", dict(add=True), (2, 1, 1, 0, 0)),
+    ("algo 1: 96 tiles of 256 -> the 128 tile", dict(algo=1), (0, 0, 1, 0, 0)),
+    ("algo 3: four waves whatever the grid", dict(algo=3), (3, 0, 1, 0, 0)),
+    ("algo 3, Cout 264: not whole 128-blocks -> eight waves", dict(algo=3, Cout=264), (2, 0, 1, 0, 0)),
+    ("T 24: 768 tiles -> four waves by shape", dict(T=24), (3, 0, 1, 0, 0)),
+    ("T 24, algo 4", dict(T=24, algo=4), (2, 0, 1, 0, 0)),
+    ("T 3: 128 tiles -> still eight waves", dict(T=3), (2, 0, 1, 0, 0)),
+    ("T 2: 64 tiles -> the implicit GEMM", dict(T=2), (0, 0, 1, 0, 0)),
+    ("M 49149 x 264, algo 1: 384 tiles of 256", dict(T=3, H=129, W=127, Cout=264, algo=1), (1, 0, 1, 0, 0)),
+    ("M 48896 x 264, algo 1: 382 tiles of 256", dict(T=2, H=191, W=128, Cout=264, algo=1), (0, 0, 1, 0, 0)),
+    ("strided: never direct", dict(stride_t=2, stride_hw=2), (0, 0, 1, 0, 0)),
+    ("strided, algo 2: refused", dict(stride_hw=2, algo=2), -2),
+    ("kernel_t 1", dict(kernel_t=1), (0, 0, 1, 0, 0)),
+    ("no bias: never direct", dict(bias=False), (0, 0, 1, 0, 0)),
+    ("depth-to-space off 1024 channels", dict(d2s=True, Cout=320), (0, 2, 1, 0, 0)),
+    ("depth-to-space at 1024 channels", dict(d2s=True, Cout=1024, residual=True), (3, 2, 1, 0, 0)),
+    ("depth-to-space + add", dict(d2s=True, Cout=1024, add=True), -1),
+    ("post_norm, Cout 128, four waves", dict(T=48, Cout=128, post_norm=1), (3, 3, 1, 0, 0)),
+    ("post_norm where no wave holds a position", dict(post_norm=1), -2),
+    ("y_norm + add, Cout 128", dict(T=48, Cout=128, post_norm=1, add=True, y_norm=True), (3, 4, 1, 0, 0)),
+    ("y_norm without post_norm", dict(y_norm=True), -1),
+    ("1024 -> 1024 at 13 x 16 x 24 with a workspace: three ranges, rows along H",
+     dict(T=13, H=16, W=24, Cin=1024, Cout=1024, workspace=3 * 4992 * 1024 * 4), (3, 6, 3, 1, 4)),
+    ("... a workspace 16 bytes short: unsplit", dict(T=13, H=16, W=24, Cin=1024, Cout=1024, workspace=3 * 4992 * 1024 * 4 - 16),
+     (2, 0, 1, 0, 0)),
+    ("... workspace_bytes without a workspace", dict(workspace_bytes_only=64), -1),
+    ("Cin 96", dict(Cin=96), -2), ("Cout 12", dict(Cout=12), -2), ("algo 5", dict(algo=5), -1), ("stride 3", dict(stride_t=3), -2),
+    ("misaligned x", dict(x_off=8), -2), ("NULL y", dict(y=False), -1), ("T 0", dict(T=0), -1),
+]
+
+
+def _conv_geometry(over):
+    from ltxmi import _lib
+    over = dict(over)
+    a = _lib.Conv3dArgs()
+    a.x, a.w, a.y, a.bias = 4096 + over.pop("x_off", 0), 8192, (12288 if over.pop("y", True) else None), \
+        (16384 if over.pop("bias", True) else None)
+    a.B, a.T, a.H, a.W, a.Cin, a.Cout, a.causal, a.pad_replicate = 1, 6, 64, 64, 64, 256, 1, 1
+    for k in ("add", "y_norm", "residual"):
+        if over.pop(k, False):
+            setattr(a, k, 20480)
+    if a.residual:
+        a.res_channels = 64
+    if "workspace" in over:
+        a.workspace, a.workspace_bytes = 24576, over.pop("workspace")
+    a.workspace_bytes = over.pop("workspace_bytes_only", a.workspace_bytes)
+    for k, v in over.items():
+        setattr(a, k, int(v))
+    return a
+
+
+@pytest.mark.parametrize("case", CONV_ROUTES, ids=lambda c: c[0])
+def test_conv3d_route_table(case):
+    """The route query reports the launch's own decision, and refuses what the launch refuses with the same status -- both
+    before anything needs a device."""
+    from ltxmi import _lib
+    what, over, want = case
+    a = _conv_geometry(over)
+    info = _lib.Conv3dRouteInfo(9, 9, 9, 9, 9)
+    got = _lib.lib.ltxmi_conv3d_route(ctypes.byref(a), ctypes.byref(info))
+    fields = (info.route, info.epilogue, info.ksplit, info.swap_hw, info.finalize_blocks)
+    if isinstance(want, int):
+        assert got == want and fields == (-1, 0, 0, 0, 0), (what, got, fields, _lib.lib.ltxmi_last_error())
+        assert _lib.lib.ltxmi_last_error()
+        assert _lib.lib.ltxmi_conv3d_ndhwc_bf16(ctypes.byref(a), None) == want
+    else:
+        assert got == 0 and fields == want, (what, got, fields, _lib.lib.ltxmi_last_error())
+    assert _lib.lib.ltxmi_conv3d_route(ctypes.byref(a), None) == -1
+
+
+def test_conv3d_route_through_ops_needs_no_device():
+    """ops.conv3d_route builds the struct ops.conv3d builds: host tensors give the geometry (never touched)."""
+    import torch
+    from ltxmi import ops
+    bf = torch.bfloat16
+    x, w, b = torch.empty(1, 13, 16, 24, 1024, dtype=bf), torch.empty(1024, 27 * 1024, dtype=bf), torch.empty(1024, dtype=bf)
+    split = dict(route=ops.CONV_DIRECT4, epilogue=6, ksplit=3, swap_hw=1, finalize_blocks=4, second_launch=False)
+    assert ops.conv3d_route(x, w, b, True, True) == split                      # with the workspace ops.conv3d would hand over
+    assert ops.conv3d_route(x, w, b, True, True, post_norm=(None, None, 1e-8)) == split
+    none = torch.empty(0, dtype=torch.uint8)
+    assert ops.conv3d_route(x, w, b, True, True, workspace=none) == dict(split, route=ops.CONV_DIRECT8, epilogue=0, ksplit=1,
+                                                                        swap_hw=0, finalize_blocks=0)
+    # unsplit, no kernel takes the norm along at this width: ops.conv3d launches it after the convolution
+    assert ops.conv3d_route(x, w, b, True, True, workspace=none, post_norm=(None, None, 1e-8))["second_launch"]
+    assert ops.conv3d_route(x, w, b, True, True, algo=1)["route"] == ops.CONV_GEMM128
+    assert ops.conv3d_route(x, w, b, True, True, stride=(2, 2, 2), algo=2) == -2
+    with pytest.raises(TypeError):
+        ops.conv3d_route(x.float(), w, b, True, True)
+
+
 def test_host_ops_refuse_cpu_tensors():
     """The product path has no CPU fallback: CPU tensors are an error, not a slow path."""
     import torch

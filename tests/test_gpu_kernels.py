@@ -485,7 +485,8 @@ def test_conv3d(causal, mode, cin, cout, shape):
 
 
 def test_conv3d_big_tile_and_add():
-    """Enough positions for the 256x256 tile path, plus the fused skip-add epilogue."""
+    """The fused skip-add epilogue at 24576 positions x 256 channels: by shape (192 direct tiles) the eight-wave direct
+    convolution.  (The implicit GEMM's 256 x 256 tile needs 384 of them: tests/test_gpu_conv_paths.py runs it.)"""
     from ltxmi import ops
     from oracle import vae as ov
     B, T, H, W, cin, cout = 1, 6, 64, 64, 64, 256
@@ -495,7 +496,10 @@ def test_conv3d_big_tile_and_add():
     skip = rnd(B, cout, T, H, W, seed=56)
     truth = ov.causal_conv3d(x.float(), {"conv.weight": w.float(), "conv.bias": b.float()}, "", False, "replicate")
     wp = w.permute(0, 2, 3, 4, 1).reshape(cout, -1).contiguous()
-    out = ops.conv3d(ndhwc(x).to(DEV), wp.to(DEV), b.to(DEV), False, True, add=ndhwc(skip).to(DEV))
+    args = (ndhwc(x).to(DEV), wp.to(DEV), b.to(DEV), False, True)
+    r = ops.conv3d_route(*args, add=ndhwc(skip).to(DEV))
+    assert (r["route"], r["epilogue"], r["ksplit"]) == (ops.CONV_DIRECT8, 1, 1), r
+    out = ops.conv3d(*args, add=ndhwc(skip).to(DEV))
     check(ncdhw(out.cpu()), truth + skip.float(), what="conv3d big + add")
 
 
@@ -1065,11 +1069,16 @@ def test_conv3d_channel_split(kind, grid, monkeypatch):
     assert want >= 2 * B * T * H * W * cout * 4 and want % (B * T * H * W * cout * 4) == 0, want
     a.post_norm = 0
 
-    def run():
-        return ops.conv3d(xd, wp, bdd, True, True, d2s=d2s, residual=res, add=add, post_norm=pn, keep_raw=keep)
+    def run(fn=ops.conv3d):
+        return fn(xd, wp, bdd, True, True, d2s=d2s, residual=res, add=add, post_norm=pn, keep_raw=keep)
 
+    r = run(ops.conv3d_route)
+    assert (r["route"], r["epilogue"], r["swap_hw"], r["finalize_blocks"], r["second_launch"]) == \
+        (ops.CONV_DIRECT4, 6, int(not narrow and kind != "add"), cout // 256, False) and r["ksplit"] == want // (B * T * H * W * cout * 4), r
     split = run()
     monkeypatch.setattr(ops, "CONV_SPLIT", False)
+    r = run(ops.conv3d_route)
+    assert r["ksplit"] == 1 and r["epilogue"] < 6 and r["second_launch"] == (pn is not None), r
     plain = run()
     torch.cuda.synchronize()
     outs = list(zip(split, plain)) if keep else [(split, plain)]
@@ -1124,11 +1133,14 @@ def test_conv3d_tiles_with_their_rows_along_h():
     w = rnd(cout, cin, 3, 3, 3, seed=151, scale=(27 * cin) ** -0.5)
     b = rnd(cout, seed=152)
     wp = w.permute(0, 2, 3, 4, 1).reshape(cout, -1).contiguous().to(DEV)
+    r = ops.conv3d_route(ndhwc(x).to(DEV), wp, b.to(DEV), True, False, algo=3)
+    assert (r["route"], r["epilogue"], r["ksplit"], r["swap_hw"]) == (ops.CONV_DIRECT4, 0, 1, 1), r
     out = ops.conv3d(ndhwc(x).to(DEV), wp, b.to(DEV), True, False, algo=3)
     truth = ov.causal_conv3d(x.float(), {"conv.weight": w.float(), "conv.bias": b.float()}, "", True, "zeros")
     check(ncdhw(out.cpu()), truth, what="tiles with rows along H vs oracle")
     xt, wt = x.transpose(3, 4).contiguous(), w.transpose(3, 4).contiguous()      # H <-> W: 24 x 16, ordinary layout (3 x 1 tiles)
     wpt = wt.permute(0, 2, 3, 4, 1).reshape(cout, -1).contiguous().to(DEV)
+    assert ops.conv3d_route(ndhwc(xt).to(DEV), wpt, b.to(DEV), True, False, algo=3)["swap_hw"] == 0
     out_t = ops.conv3d(ndhwc(xt).to(DEV), wpt, b.to(DEV), True, False, algo=3).transpose(2, 3)
     d = (out_t.float() - out.float()).abs()
     assert bool((d <= out.float().abs() * 2.0 ** -7 + 1e-2).all()), float(d.max())
