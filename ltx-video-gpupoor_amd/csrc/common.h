@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/ltxmi.h"
 
 namespace ltxmi {
@@ -97,22 +99,16 @@ int check_launch(const char* what);
 //   device_cu_count: CUs of the current device (cached per device), <= 0 on failure.
 int reserve_lds(const void* kernel, int bytes, unsigned long long* done, const char* what);
 int device_cu_count(const char* what);
-// ltxmi_conv3d_ndhwc_bf16 (conv_direct.hip): how one call runs, worked out once from its arguments by conv3d_plan; the launch acts
-// on it and ltxmi_conv3d_workspace_bytes / ltxmi_conv3d_fuses_post_norm return its fields.  CONV_REFUSED: algo asks for the
-// direct convolution, which does not take the shape.
-enum ConvRoute : int { CONV_GEMM128, CONV_GEMM256, CONV_DIRECT8, CONV_DIRECT4, CONV_REFUSED };
-struct ConvPlan {
-    int kt, sT, sHW, tpad;              // kernel frames, time / space strides, frames of padding in front
-    int oT, oH, oW; int64_t M;          // output grid, M = B oT oH oW positions
-    ConvRoute route;                    // the implicit GEMM (gemm.hip) with 128- / 256-wide tiles, the eight- / four-wave direct form
-    int epi;                            // 0 plain, 1 + add, 2 depth-to-space; four-wave form also 3 .. 5 = the same + post_norm,
-                                        // 6 = fp32 partial sums of a channel split (the finalising pass applies the epilogue)
-    int swap, ksplit, tiles_t, tiles_8, tiles_16, tiles_n;    // direct forms: see conv3d_plan
-    int64_t grid, split_bytes;          // workgroups of ONE channel range; workspace the split needs (0: no split pays)
-    bool fuses_post_norm;               // post_norm = 1 would be applied in the epilogue
-};
-int conv3d_gemm_tile(int64_t M, int Cout);     // gemm.hip: the implicit GEMM's tile (128 or 256) for M positions x Cout
-int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream);
+// One launch of a kernel instance that may need more dynamic LDS than the default: reserve it (once per instance and device --
+// the mask is this instantiation's own), launch, check_launch.  Returns LTXMI_OK or the negative status with the error text set.
+template <int E> using epi_t = std::integral_constant<int, E>;     // an epilogue as a tag: run-time epi -> kernel instance
+template <auto Kernel, class Params>
+int launch_with_lds(const Params& p, dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const char* what) {
+    static unsigned long long lds_done = 0;
+    if (const int rc = reserve_lds((const void*)Kernel, lds_bytes, &lds_done, what)) return rc;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, p);
+    return check_launch(what);
+}
 
 }  // namespace ltxmi
 

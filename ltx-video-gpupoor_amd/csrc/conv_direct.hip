@@ -10,29 +10,10 @@
 //                  row & 7 (on the DMA source side); weights 2 stages x 128 rows x 128 B = 32 KB
 //   per chunk    : halo DMA (90 pieces), then per tap: next tap's weight DMA (2 pieces per wave) || fragment
 //                  reads (A rows = 16 x-consecutive halo rows at a wave-uniform tap offset) || 32 MFMAs; barrier
-#include <math.h>
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "common.h"
+#include "conv.h"
+#include "epilogue.h"
 
 namespace ltxmi {
-
-struct ConvDirectP {
-    const uint16_t* x; const uint16_t* w; const uint16_t* bias; uint16_t* y; const uint16_t* add;
-    const uint16_t* res; int res_ch;            // depth-to-space residual (x itself) or NULL
-    int B, T, H, W, Cin, Cout;
-    int tpad, pad_replicate, tzero;
-    int tiles_t, tiles_y, tiles_x, tiles_n;
-    const float* post_scale; const float* post_shift; float post_eps;      // EPI >= 3 only
-    uint16_t* y2;                                                          // EPI 4 / 5: the activated second output
-    // four-wave form only.  swap_hw: the tile's 16-position rows run along H and its 8 rows along W (W = 24 is 1.5 tiles of 16,
-    // H = 16 exactly one: 21 tiles instead of 28 at the 1024-channel stage).  ksplit > 1: the input channels are cut into ksplit
-    // ranges, one workgroup each (grid x ksplit), whose fp32 partial sums go to `part` [ksplit][B T H W][Cout] (EPI 6, no bias);
-    // conv_split_finalize_kernel adds them up and applies the epilogue
-    int swap_hw, ksplit; float* part;
-};
 
 __device__ __attribute__((aligned(16))) uint32_t g_zero_page_cd[16];
 
@@ -53,23 +34,14 @@ __device__ unsigned long long* g_conv_stamps = nullptr;
 #define CSTAMP(i) do { } while (0)
 #endif
 
-constexpr int CD_TT = 2, CD_TY = 8, CD_TX = 16;
-constexpr int CD_HT = CD_TT + 2, CD_HY = CD_TY + 2, CD_HX = CD_TX + 2;
-constexpr int CD_HALO_ROWS = CD_HT * CD_HY * CD_HX;            // 720
-constexpr int CD_HALO_BYTES = CD_HALO_ROWS * 128;               // 92160
-constexpr int CD_W_BYTES = 128 * 128;                           // one tap: 128 output channels x 64 input channels
-constexpr int CD_WSTAGES = 3;
-constexpr int CD_ROWTAB_BYTES = CD_HALO_ROWS * 4;               // per halo row: byte offset of its source row (or the 'zero' sentinel)
-constexpr int CD_CTLTAB_BYTES = 8 * 27 * 8;                     // per (wave, tap): two packed control words
-constexpr int CD_SMEM = CD_HALO_BYTES + CD_WSTAGES * CD_W_BYTES + CD_ROWTAB_BYTES + CD_CTLTAB_BYTES; 
-
 // EPI: 0 plain store, 1 y = conv + add, 2 depth-to-space store (+ residual), as the implicit-GEMM kernel's epilogues
 template <int EPI>
 __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     constexpr bool ADD = (EPI == 1), D2S = (EPI == 2);
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    using G = ConvGeo8;
     char* halo = smem;
-    char* wst = smem + CD_HALO_BYTES;
+    char* wst = smem + G::HALO_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // waves 0..3 (one per SIMD) take the first 64 output channels of the block, waves 4..7 the second 64: when the block's
@@ -77,13 +49,8 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     const int wm = wave & 3, wn = wave >> 2;
 
     // ---- tile: blockIdx.x -> (n block fastest, then x, y, t, b): the n blocks of a position tile are neighbours
-    int id = blockIdx.x;
-    const int nb = id % p.tiles_n; id /= p.tiles_n;
-    const int tx = id % p.tiles_x; id /= p.tiles_x;
-    const int ty = id % p.tiles_y; id /= p.tiles_y;
-    const int tt = id % p.tiles_t;
-    const int b = id / p.tiles_t;
-    const int t0 = tt * CD_TT, y0 = ty * CD_TY, x0 = tx * CD_TX, n0 = nb * 128;
+    const ConvTile tile = conv_tile<G>(blockIdx.x, p.tiles_n, p.tiles_x, p.tiles_y, p.tiles_t, p.B);
+    const int b = tile.b, t0 = tile.t0, y0 = tile.y0, x0 = tile.x0, n0 = tile.n0;
 
     // ---- halo loader: piece q = rows 8q .. 8q+7; lane -> (row 8q + lane>>3, LDS slot lane&7, source slot ^ row&7).
     // Where a halo row comes from depends on the tile only, not on the 64-channel chunk: the byte offset of every halo row's
@@ -95,11 +62,11 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     const int64_t x_bytes = (int64_t)p.B * p.T * p.H * p.W * p.Cin * 2;
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.x, 0, (int)(x_bytes < 0x7ffffff0ll ? x_bytes : 0x7ffffff0ll), 0x00020000);
-    uint32_t* rowtab = (uint32_t*)(smem + CD_HALO_BYTES + CD_WSTAGES * CD_W_BYTES);
+    uint32_t* rowtab = (uint32_t*)(smem + G::ROWTAB_OFF);
     {
         const int64_t xb = (int64_t)b * p.T * p.H * p.W * p.Cin;
-        for (int r = tid; r < CD_HALO_ROWS; r += 512) {
-            const int hx = r % CD_HX, hy = (r / CD_HX) % CD_HY, ht = r / (CD_HX * CD_HY);
+        for (int r = tid; r < G::HALO_ROWS; r += 512) {
+            const int hx = r % G::HX, hy = (r / G::HX) % G::HY, ht = r / (G::HX * G::HY);
             int ti = t0 + ht - p.tpad, yi = y0 + hy - 1, xi = x0 + hx - 1;
             const bool toob = (ti < 0) | (ti >= p.T);
             const bool oob = (yi < 0) | (yi >= p.H) | (xi < 0) | (xi >= p.W);
@@ -120,21 +87,11 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     // NEXT chunk's rows 0..175 (pieces 0..21) under taps 9..11 and its rows 176..359 (pieces 22..44) under taps 18..21.  A
     // chunk boundary has no load phase of its own (round 2: 1950 cycles of issue + 2200 of waiting per chunk with the matrix
     // pipe idle); only the first chunk's planes 0 and 1 are loaded in front of the tap stream.
-    constexpr int Q_PLANE0 = 22, Q_PLANE1 = 45, Q_END = CD_HALO_ROWS / 8;
-    // Source row offset of a tap's piece: read from the table at the end of the tap before (unconditionally), turned into the
-    // lane's offset behind that tap's second MFMA block, used at its end.  The read is issued from inline asm and waited for by
-    // hand: as a C++ load hipcc put s_waitcnt lgkmcnt(0) in front of it (at the end of every tap, behind the fragment reads
-    // just issued).  An LDS read hipcc does not know about only makes its own counted waits more conservative: LDS
-    // operations complete in order.
+    // Source row offset of a tap's piece: read from the table at the end of the tap before (a hidden read: conv.h), turned into
+    // the lane's offset behind that tap's second MFMA block, used at its end
     uint32_t hoff_nx = 0;
     const uint32_t rowtab_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)rowtab) + (uint32_t)(lane >> 3) * 4;
-    auto read_hoff = [&](int q) __attribute__((always_inline)) {
-        const uint32_t a = rowtab_lds + (uint32_t)(q * 32);
-        asm volatile("ds_read_b32 %0, %1" : "=v"(hoff_nx) : "v"(a) : "memory");
-    };
-    // ---- weights of one tap and chunk: rows n0 .. n0+127 of w [Cout, 27*Cin], 64 channels at (tap*Cin + c0), through a
-    // descriptor over the block's rows (rows past Cout are out of range and arrive as zeros: never stored), so that a piece is
-    // one VALU add + one buffer_load ... lds with the (tap, chunk) offset in a scalar.
+    // ---- weights of one tap and chunk: 64 channels at (tap*Cin + c0) of the block's rows
     const int w_row_bytes = 27 * p.Cin * 2;
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(p.w + (int64_t)n0 * 27 * p.Cin), 0, min(128, p.Cout - n0) * w_row_bytes, 0x00020000);
@@ -142,27 +99,11 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     const int wp0 = wave * 2;
     const uint32_t woff0 = (uint32_t)((wp0 * 8 + (lane >> 3)) * w_row_bytes + (((lane & 7) ^ ((lane >> 3) & 7)) << 4));
     auto load_w_piece = [&](int stage, int soff, int j) __attribute__((always_inline)) {   // piece j of this wave
-        blds16(w_rsrc, wst + stage * CD_W_BYTES + (wp0 + j) * 1024, woff0 + (uint32_t)(j * 8 * w_row_bytes), soff);
+        blds16(w_rsrc, wst + stage * G::W_BYTES + (wp0 + j) * 1024, woff0 + (uint32_t)(j * 8 * w_row_bytes), soff);
     };
 
-    // ---- what a tap of the (chunk, tap) stream does besides its MFMAs -- all wave-uniform, all a function of (tap, chunk).
-    // Scalar instructions are NOT free beside MFMAs here: both waves of a SIMD pair run the same code at the same time, and a
-    // wave that issues a scalar instruction issues no MFMA (tools/ubench/conv_loop.hip: a bare loop of this tap's 2 x 32 MFMAs
-    // runs at 1032 cycles per tap; with the fragment reads, their address arithmetic and the barrier 1196; with ~140 dependent
-    // scalar instructions behind block 2 it takes 1780).  So the control of the 27 taps is worked out ONCE per tile into a table
-    // in LDS (two packed words per (wave, tap)); a tap reads the entry of the tap after the next with one hidden ds_read_b64 at
-    // its end, and the tap in between unpacks it behind its third MFMA block: ~20 scalar instructions per tap instead of the ~85
-    // that recomputing it from (tap, chunk) took (measured on the way: recomputed at the top of the tap -5 %, behind block 2
-    // +2.0..2.7 % over round 2's kernel, behind block 0 / 1 / 3 -3.5 / -2.2 / -2.0 %: profiles/r03_conv_stream.log).
-    struct Ctl {
-        int w_soff, w_stage;     // weights two taps ahead in the stream: scalar byte offset (< 0: nothing to issue), stage
-        int h_q, h_soff;         // this tap's halo piece (-1: none) and its chunk's byte offset
-        int n_off, n_stage;      // next tap: halo row offset of its (dt, dy, dx), weight stage
-        int n_q;                 // next tap's piece slot in the row table (clamped; whether there is a piece: its own h_q)
-    };
-    // word 0: byte offset of tap + 2's weights inside a weight row, relative to its chunk; bit 31: that tap belongs to the NEXT chunk
-    // word 1: n_off [0,9) | w_stage [9,11) | n_stage [11,13) | halo piece [13,21) (0xff: none) | piece of the chunk itself [21] | n_q [22,29)
-    uint32_t* ctltab = (uint32_t*)(smem + CD_HALO_BYTES + CD_WSTAGES * CD_W_BYTES + CD_ROWTAB_BYTES);
+    // ---- the control table (conv.h, ConvCtl: why, and the packing of its two words per (wave, tap))
+    uint32_t* ctltab = (uint32_t*)(smem + G::CTLTAB_OFF);
     if (tid < 8 * 27) {
         const int w = tid / 27, tap = tid - w * 27;
         auto piece_slot = [](int t) { return t <= 6 ? t + 5 : t <= 11 ? t - 9 : t - 16; };     // (meaningful inside the three windows)
@@ -170,39 +111,22 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
         const int t2 = wrap2 ? tap - 25 : tap + 2;
         const bool own = tap <= 6;                                                 // the chunk's own planes 2 and 3
         const bool win = own | ((tap >= 9) & (tap <= 11)) | ((tap >= 18) & (tap <= 21));
-        const int lo = own ? Q_PLANE1 : tap <= 11 ? 0 : Q_PLANE0, hi = own ? Q_END : tap <= 11 ? Q_PLANE0 : Q_PLANE1;
+        const int lo = own ? G::Q_PLANE1 : tap <= 11 ? 0 : G::Q_PLANE0, hi = own ? G::Q_END : tap <= 11 ? G::Q_PLANE0 : G::Q_PLANE1;
         const int q = w + 8 * piece_slot(tap);
         const int hq = (win & (q >= lo) & (q < hi)) ? q : 0xff;
         const int tn = tap < 26 ? tap + 1 : 0;                                     // behind a chunk's last tap: the next chunk's tap 0
-        const int n_off = ((tn / 9) * CD_HY + (tn / 3) % 3) * CD_HX + tn % 3;
+        const int n_off = ((tn / 9) * G::HY + (tn / 3) % 3) * G::HX + tn % 3;
         const int qn = w + 8 * piece_slot(tn);
-        const int n_q = qn < 0 ? 0 : qn < Q_END ? qn : Q_END - 1;
+        const int n_q = qn < 0 ? 0 : qn < G::Q_END ? qn : G::Q_END - 1;
         ctltab[tid * 2] = (uint32_t)(t2 * p.Cin * 2) | (wrap2 ? 0x80000000u : 0u);
-        ctltab[tid * 2 + 1] = (uint32_t)n_off | (uint32_t)(t2 % CD_WSTAGES) << 9 | (uint32_t)(tn % CD_WSTAGES) << 11 | (uint32_t)hq << 13 |
+        ctltab[tid * 2 + 1] = (uint32_t)n_off | (uint32_t)(t2 % G::WSTAGES) << 9 | (uint32_t)(tn % G::WSTAGES) << 11 | (uint32_t)hq << 13 |
                               (own ? 1u << 21 : 0u) | (uint32_t)n_q << 22;
     }
     u32x2 cw_nx = {0u, 0u};                                                       // the packed entry in flight
     const uint32_t ctltab_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)ctltab) + (uint32_t)(wave * 27 * 8);
-    auto read_ctl = [&](int tap) __attribute__((always_inline)) {
-        const uint32_t a = ctltab_lds + (uint32_t)(tap * 8);
-        asm volatile("ds_read_b64 %0, %1" : "=v"(cw_nx) : "v"(a) : "memory");
-    };
-    auto unpack_ctl = [&](uint32_t d0, uint32_t d1, int c0) __attribute__((always_inline)) -> Ctl {
-        Ctl k;
-        const int c_next = c0 + 64 < p.Cin ? c0 + 64 : -1;
-        const int c2 = (int)d0 < 0 ? c_next : c0;
-        k.w_soff = c2 >= 0 ? (int)(d0 & 0x7fffffffu) + c2 * 2 : -1;
-        k.n_off = (int)(d1 & 0x1ffu);
-        k.w_stage = (int)((d1 >> 9) & 3u);
-        k.n_stage = (int)((d1 >> 11) & 3u);
-        const int hq = (int)((d1 >> 13) & 0xffu);
-        const int c = ((d1 >> 21) & 1u) ? c0 : c_next;
-        k.h_q = ((hq != 0xff) & (c >= 0)) ? hq : -1;
-        k.h_soff = c * 2;
-        k.n_q = (int)((d1 >> 22) & 0x7fu);
-        return k;
-    };
 
+    // (through this lambda, not called in place: in place instance <2> gains three s_waitcnt)
+    auto unpack_ctl = [&](uint32_t d0, uint32_t d1, int c0) __attribute__((always_inline)) { return conv_unpack_ctl<G>(d0, d1, c0, p.Cin); };
     // ---- fragment geometry.  A block i of this wave = positions wm*64 + i*16 + (lane & 15): one (t, y) row of
     // the tile, x = lane & 15, so its halo row at tap (dt, dy, dx) is R(i, tap) + (lane & 15), R wave-uniform.
     const int frow = lane & 15, fchunk = lane >> 4;
@@ -223,11 +147,11 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     auto read_frags = [&](auto set_tag, int tap) {
         constexpr int S = decltype(set_tag)::value;
         const int dt = tap / 9, dy = (tap / 3) % 3, dx = tap % 3;
-        const char* ws = wst + (tap % CD_WSTAGES) * CD_W_BYTES;     // (only called for tap 0 of the stream)
+        const char* ws = wst + (tap % G::WSTAGES) * G::W_BYTES;     // (only called for tap 0 of the stream)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int blk = wm * 4 + i;                                  // (t, y) row of the tile
-            const int row = (((blk >> 3) + dt) * CD_HY + ((blk & 7) + dy)) * CD_HX + dx + frow;
+            const int row = (((blk >> 3) + dt) * G::HY + ((blk & 7) + dy)) * G::HX + dx + frow;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
                 af[S][i][ks] = *(const bf16x8*)(halo + row * 128 + (((fchunk + 4 * ks) ^ (row & 7)) << 4));
@@ -274,7 +198,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     // any more; they are never used: no branch sits between the MFMA blocks)
     const bool active = n0 + wn * 64 < p.Cout;
     int s_tap = 0, s_c0 = 0;                                     // the stream position
-    Ctl cur;                                                     // (set in front of the stream, below)
+    ConvCtl cur;                                                     // (set in front of the stream, below)
     auto tap_body = [&](auto cur_tag, auto nxt_tag) __attribute__((always_inline)) {
         CSTAMP(3);
         if (cur.w_soff >= 0) {
@@ -285,7 +209,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
         // the stream position after this tap
         int tap1 = s_tap + 1, c01 = s_c0;
         if (tap1 == 27) { tap1 = 0; c01 += 64; }
-        Ctl nxt;
+        ConvCtl nxt;
         uint32_t hfin;
         if (active) {
             // The 16 fragment reads of tap + 1 are NOT issued as a burst in front of this tap's MFMAs: right after the
@@ -294,7 +218,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
             // Each position block's 8 MFMAs go first, the reads of the next tap's same block (and one weight block) follow.
             constexpr int S = decltype(cur_tag)::value;          // register sets of this tap's / the next tap's fragments
             constexpr int N = decltype(nxt_tag)::value;
-            const char* ws = wst + cur.n_stage * CD_W_BYTES;
+            const char* ws = wst + cur.n_stage * G::W_BYTES;
             u32x2 cw;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -304,7 +228,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
                     for (int j = 0; j < 4; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[S][j][ks], af[S][i][ks], acc[i][j], 0, 0, 0);
                 const int blk = wm * 4 + i;                                      // (t, y) row of the tile
-                const int row = ((blk >> 3) * CD_HY + (blk & 7)) * CD_HX + cur.n_off + frow;
+                const int row = ((blk >> 3) * G::HY + (blk & 7)) * G::HX + cur.n_off + frow;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     af[N][i][ks] = *(const bf16x8*)(halo + row * 128 + (((fchunk + 4 * ks) ^ (row & 7)) << 4));
@@ -336,8 +260,8 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
             asm volatile("" : "+s"(d0), "+s"(d1), "+s"(c01));
             nxt = unpack_ctl((uint32_t)d0, (uint32_t)d1, c01);
         }
-        read_hoff(cur.n_q);
-        read_ctl(tap1 == 26 ? 0 : tap1 + 1);                     // the entry of the tap after the next
+        conv_read_hoff<G>(hoff_nx, rowtab_lds, cur.n_q);
+        conv_read_ctl(cw_nx, ctltab_lds, tap1 == 26 ? 0 : tap1 + 1);                     // the entry of the tap after the next
         // this tap's halo piece goes out as the wave's youngest request: it may stay in flight across the barrier (the wait of
         // the following tap covers it)
         if (cur.h_q >= 0) blds16(x_rsrc, halo + cur.h_q * 1024, hfin, cur.h_soff);
@@ -352,9 +276,9 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     CSTAMP(3);
     __syncthreads();                                             // the row table is complete
 #pragma unroll
-    for (int k = 0; k < (Q_PLANE1 + 7) / 8; ++k) {
+    for (int k = 0; k < (G::Q_PLANE1 + 7) / 8; ++k) {
         const int q = wave + 8 * k;
-        if (q < Q_PLANE1) blds16(x_rsrc, halo + q * 1024, rowtab[q * 8 + (lane >> 3)] + hslot, 0);
+        if (q < G::Q_PLANE1) blds16(x_rsrc, halo + q * 1024, rowtab[q * 8 + (lane >> 3)] + hslot, 0);
     }
 #pragma unroll
     for (int j = 0; j < WPP; ++j) {
@@ -370,8 +294,8 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
     // entry and tap 1's control
     cur = unpack_ctl((uint32_t)__builtin_amdgcn_readfirstlane((int)ctltab[wave * 54]),
                      (uint32_t)__builtin_amdgcn_readfirstlane((int)ctltab[wave * 54 + 1]), 0);
-    read_hoff(wave + 40 < Q_END ? wave + 40 : Q_END - 1);        // (tap 0's piece slot: wave + 8 * 5)
-    read_ctl(1);
+    conv_read_hoff<G>(hoff_nx, rowtab_lds, wave + 40 < G::Q_END ? wave + 40 : G::Q_END - 1);        // (tap 0's piece slot: wave + 8 * 5)
+    conv_read_ctl(cw_nx, ctltab_lds, 1);
     // The (chunk, tap) stream is walked two taps at a time (the fragment register sets alternate per tap; a chunk has 27 taps,
     // so the pairs straddle the chunk boundaries)
     {
@@ -424,8 +348,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                v[0] += bf_lo(bias_v[j][0]); v[1] += bf_hi(bias_v[j][0]);
-                v[2] += bf_lo(bias_v[j][1]); v[3] += bf_hi(bias_v[j][1]);
+                add_bf16x4(v, bias_v[j]);
                 if (D2S && p.res) {
                     // x_in = repeat(pixel_shuffle(x)): channel c' <- x[(c' mod (Cres/8)) * 8 + pp]   (gemm.hip, EPI_D2S)
                     const int pos = wm * 64 + i * 16 + frow;
@@ -443,9 +366,7 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
                     v[0] += bf_lo(add_f[i][j][0]); v[1] += bf_hi(add_f[i][j][0]);
                     v[2] += bf_lo(add_f[i][j][1]); v[3] += bf_hi(add_f[i][j][1]);
                 }
-                u32x2 o;
-                o[0] = pack_bf16(v[0], v[1]);
-                o[1] = pack_bf16(v[2], v[3]);
+                const u32x2 o = pack_bf16x4(v);
                 const int chunk = j * 2 + (lane >> 5);
                 *(u32x2*)(scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4) + ((lane >> 4) & 1) * 8) = o;
             }
@@ -494,22 +415,6 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
 // as a SECOND output, 6 fp32 partial sums of a range of input channels), tiles whose 16-position rows run along H instead of W,
 // and the split over the input channels (ConvDirectP::swap_hw / ksplit, conv3d_plan, conv_split_finalize_kernel below).
 namespace v3 {
-constexpr int TT = 2, TY = 8, TX = 16;
-constexpr int HT = TT + 2, HY = TY + 2, HX = TX + 2;
-constexpr int PLANE_ROWS = HY * HX;                    // 180
-constexpr int PLANE_STRIDE = 192;                      // ... in whole 16-row pieces
-constexpr int HALO_ROWS = HT * PLANE_STRIDE;           // 768
-constexpr int ROW_B = 64;                              // 32 input channels
-constexpr int HALO_BYTES = HALO_ROWS * ROW_B;          // 49152
-constexpr int W_BYTES = 128 * ROW_B;                   // one tap: 128 output channels x 32 input channels
-constexpr int WSTAGES = 3;
-constexpr int ROWTAB_BYTES = HALO_ROWS * 4;
-constexpr int CTLTAB_BYTES = 4 * 27 * 8;
-constexpr int SMEM = HALO_BYTES + WSTAGES * W_BYTES + ROWTAB_BYTES + CTLTAB_BYTES;   // 77664
-constexpr int Q_PLANE0 = PLANE_STRIDE / 16, Q_PLANE1 = 2 * Q_PLANE0, Q_END = HALO_ROWS / 16;   // 12, 24, 48 pieces of 16 rows
-
-__device__ __forceinline__ int swz(int c, int r) { return c ^ (((r >> 2) & 1) << 1); }       // slot of source chunk c in LDS row r
-
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p) {
     // EPI 4 / 5 = EPI 1 / 2 with TWO outputs: y as EPI 1 / 2 store it, and y2 = silu(pixelnorm(y) (1 + scale) + shift) computed from
@@ -520,19 +425,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
     constexpr bool DUAL = (EPI == 4 || EPI == 5);
     constexpr bool ADD = (EPI == 1 || EPI == 4), D2S = (EPI == 2 || EPI == 5), PNORM = (EPI == 3 || DUAL);
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    using G = ConvGeo4;
     char* halo = smem;
-    char* wst = smem + HALO_BYTES;
+    char* wst = smem + G::HALO_BYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // = the wave's position group (64 positions)
 
-    int id = blockIdx.x;
-    const int nb = id % p.tiles_n; id /= p.tiles_n;
-    const int tx = id % p.tiles_x; id /= p.tiles_x;
-    const int ty = id % p.tiles_y; id /= p.tiles_y;
-    const int tt = id % p.tiles_t; id /= p.tiles_t;
-    const int b = id % p.B;
-    const int ks = id / p.B;                                          // channel range of this workgroup (0 unless ksplit > 1)
-    const int t0 = tt * TT, y0 = ty * TY, x0 = tx * TX, n0 = nb * 128;     // y0: the tile's 8-row direction, x0: its 16-position one
+    const ConvTile tile = conv_tile<G>(blockIdx.x, p.tiles_n, p.tiles_x, p.tiles_y, p.tiles_t, p.B);
+    const int b = tile.b, ks = tile.ks, t0 = tile.t0, y0 = tile.y0, x0 = tile.x0, n0 = tile.n0;
     // tile coordinates -> image coordinates (swap_hw: the 16-position direction is H)
     const bool swp = p.swap_hw != 0;
     auto img_y = [&](int i8, int i16) __attribute__((always_inline)) { return swp ? x0 + i16 : y0 + i8; };
@@ -547,12 +447,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
     const int64_t x_bytes = (int64_t)p.B * p.T * p.H * p.W * p.Cin * 2;
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.x, 0, (int)(x_bytes < 0x7ffffff0ll ? x_bytes : 0x7ffffff0ll), 0x00020000);
-    uint32_t* rowtab = (uint32_t*)(smem + HALO_BYTES + WSTAGES * W_BYTES);
+    uint32_t* rowtab = (uint32_t*)(smem + G::ROWTAB_OFF);
     {
         const int64_t xb = (int64_t)b * p.T * p.H * p.W * p.Cin;
-        for (int r = tid; r < HALO_ROWS; r += 256) {
-            const int ht = r / PLANE_STRIDE, rr = r - ht * PLANE_STRIDE;
-            const int hy = rr / HX, hx = rr - hy * HX;
+        for (int r = tid; r < G::HALO_ROWS; r += 256) {
+            const int ht = r / G::PLANE_STRIDE, rr = r - ht * G::PLANE_STRIDE;
+            const int hy = rr / G::HX, hx = rr - hy * G::HX;
             int ti = t0 + ht - p.tpad, yi = img_y(hy - 1, hx - 1), xi = img_x(hy - 1, hx - 1);
             const bool toob = (ti < 0) | (ti >= p.T);
             const bool oob = (yi < 0) | (yi >= p.H) | (xi < 0) | (xi >= p.W);
@@ -560,12 +460,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
             yi = yi < 0 ? 0 : (yi >= p.H ? p.H - 1 : yi);
             xi = xi < 0 ? 0 : (xi >= p.W ? p.W - 1 : xi);
             const int64_t e = xb + ((int64_t)(ti * p.H + yi) * p.W + xi) * p.Cin;
-            const bool zero = (oob && !p.pad_replicate) | (toob && p.tzero) | (rr >= PLANE_ROWS);
+            const bool zero = (oob && !p.pad_replicate) | (toob && p.tzero) | (rr >= G::PLANE_ROWS);
             rowtab[r] = zero ? 0x7ffffff0u : (uint32_t)(e * 2);
         }
     }
     // ---- control table, per (wave, tap) -- see the kernel above
-    uint32_t* ctltab = (uint32_t*)(smem + HALO_BYTES + WSTAGES * W_BYTES + ROWTAB_BYTES);
+    uint32_t* ctltab = (uint32_t*)(smem + G::CTLTAB_OFF);
     if (tid < 4 * 27) {
         const int w = tid / 27, tap = tid - w * 27;
         // piece slots of a wave: its own planes 2 / 3 (24 pieces, 6 per wave) under taps 0..5, the next chunk's plane 0 (12
@@ -575,66 +475,37 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
         const int t2 = wrap2 ? tap - 25 : tap + 2;
         const bool own = tap <= 5;
         const bool win = own | ((tap >= 9) & (tap <= 11)) | ((tap >= 18) & (tap <= 20));
-        const int lo = own ? Q_PLANE1 : tap <= 11 ? 0 : Q_PLANE0, hi = own ? Q_END : tap <= 11 ? Q_PLANE0 : Q_PLANE1;
+        const int lo = own ? G::Q_PLANE1 : tap <= 11 ? 0 : G::Q_PLANE0, hi = own ? G::Q_END : tap <= 11 ? G::Q_PLANE0 : G::Q_PLANE1;
         const int q = w + 4 * piece_slot(tap);
         const int hq = (win & (q >= lo) & (q < hi)) ? q : 0xff;
         const int tn = tap < 26 ? tap + 1 : 0;
         // (the tap's dy runs along H, its dx along W: with swap_hw those are the halo's 16-position / 8-row directions)
-        const int n_off = (tn / 9) * PLANE_STRIDE + (swp ? (tn % 3) * HX + (tn / 3) % 3 : ((tn / 3) % 3) * HX + tn % 3);
+        const int n_off = (tn / 9) * G::PLANE_STRIDE + (swp ? (tn % 3) * G::HX + (tn / 3) % 3 : ((tn / 3) % 3) * G::HX + tn % 3);
         const int qn = w + 4 * piece_slot(tn);
-        const int n_q = qn < 0 ? 0 : qn < Q_END ? qn : Q_END - 1;
+        const int n_q = qn < 0 ? 0 : qn < G::Q_END ? qn : G::Q_END - 1;
         ctltab[tid * 2] = (uint32_t)(t2 * p.Cin * 2) | (wrap2 ? 0x80000000u : 0u);
-        ctltab[tid * 2 + 1] = (uint32_t)n_off | (uint32_t)(t2 % WSTAGES) << 9 | (uint32_t)(tn % WSTAGES) << 11 | (uint32_t)hq << 13 |
+        ctltab[tid * 2 + 1] = (uint32_t)n_off | (uint32_t)(t2 % G::WSTAGES) << 9 | (uint32_t)(tn % G::WSTAGES) << 11 | (uint32_t)hq << 13 |
                               (own ? 1u << 21 : 0u) | (uint32_t)n_q << 22;
     }
-    struct Ctl {
-        int w_soff, w_stage;
-        int h_q, h_soff;
-        int n_off, n_stage;
-        int n_q;
-    };
     u32x2 cw_nx = {0u, 0u};
     const uint32_t ctltab_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)ctltab) + (uint32_t)(wave * 27 * 8);
-    auto read_ctl = [&](int tap) __attribute__((always_inline)) {
-        const uint32_t a = ctltab_lds + (uint32_t)(tap * 8);
-        asm volatile("ds_read_b64 %0, %1" : "=v"(cw_nx) : "v"(a) : "memory");
-    };
-    auto unpack_ctl = [&](uint32_t d0, uint32_t d1, int c0) __attribute__((always_inline)) -> Ctl {
-        Ctl k;
-        const int c_next = c0 + 32 < c_end ? c0 + 32 : -1;
-        const int c2 = (int)d0 < 0 ? c_next : c0;
-        k.w_soff = c2 >= 0 ? (int)(d0 & 0x7fffffffu) + c2 * 2 : -1;
-        k.n_off = (int)(d1 & 0x1ffu);
-        k.w_stage = (int)((d1 >> 9) & 3u);
-        k.n_stage = (int)((d1 >> 11) & 3u);
-        const int hq = (int)((d1 >> 13) & 0xffu);
-        const int c = ((d1 >> 21) & 1u) ? c0 : c_next;
-        k.h_q = ((hq != 0xff) & (c >= 0)) ? hq : -1;
-        k.h_soff = c * 2;
-        k.n_q = (int)((d1 >> 22) & 0x7fu);
-        return k;
-    };
     // a piece = 16 rows x 64 B: lane -> (row lane >> 2, LDS slot lane & 3); (row >> 2) & 1 of a lane's row is (lane >> 4) & 1
     const uint32_t hslot = (uint32_t)(((lane & 3) ^ (((lane >> 4) & 1) << 1)) << 4);
     uint32_t hoff_nx = 0;
     const uint32_t rowtab_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)rowtab) + (uint32_t)(lane >> 2) * 4;
-    auto read_hoff = [&](int q) __attribute__((always_inline)) {
-        const uint32_t a = rowtab_lds + (uint32_t)(q * 64);
-        asm volatile("ds_read_b32 %0, %1" : "=v"(hoff_nx) : "v"(a) : "memory");
-    };
     // ---- weights: two pieces per wave and tap (rows 32 wave .. 32 wave + 31 of the block's 128)
     const int w_row_bytes = 27 * p.Cin * 2;
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(p.w + (int64_t)n0 * 27 * p.Cin), 0, min(128, p.Cout - n0) * w_row_bytes, 0x00020000);
     const uint32_t woff0 = (uint32_t)((wave * 32 + (lane >> 2)) * w_row_bytes) + hslot;
     auto load_w = [&](int stage, int soff) __attribute__((always_inline)) {
-        blds16(w_rsrc, wst + stage * W_BYTES + (wave * 2) * 1024, woff0, soff);
-        blds16(w_rsrc, wst + stage * W_BYTES + (wave * 2 + 1) * 1024, woff0 + (uint32_t)(16 * w_row_bytes), soff);
+        blds16(w_rsrc, wst + stage * G::W_BYTES + (wave * 2) * 1024, woff0, soff);
+        blds16(w_rsrc, wst + stage * G::W_BYTES + (wave * 2 + 1) * 1024, woff0 + (uint32_t)(16 * w_row_bytes), soff);
     };
 
     // ---- fragment geometry: position block i of this wave = positions wave*64 + i*16 + (lane & 15) = one (t, y) row
     const int frow = lane & 15, fchunk = lane >> 4;
-    const int b_off0 = frow * ROW_B + (swz(fchunk, frow) << 4);            // channel block j: + j * 1024
+    const int b_off0 = frow * G::ROW_B + (G::swz(fchunk, frow) << 4);            // channel block j: + j * 1024
     f32x4 acc[4][8];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -643,27 +514,27 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
     bf16x8 af[2][4], bfr[8];
     auto a_addr = [&](int i, int n_off) __attribute__((always_inline)) -> const char* {
         const int blk = wave * 4 + i;
-        const int row = (blk >> 3) * PLANE_STRIDE + (blk & 7) * HX + n_off + frow;
-        return halo + row * ROW_B + (swz(fchunk, row) << 4);
+        const int row = (blk >> 3) * G::PLANE_STRIDE + (blk & 7) * G::HX + n_off + frow;
+        return halo + row * G::ROW_B + (G::swz(fchunk, row) << 4);
     };
     using s0_t = std::integral_constant<int, 0>;
     using s1_t = std::integral_constant<int, 1>;
-    auto sync_all = [&](bool keep1) {
+    auto sync_all = [&](bool keep1) {                           // (see the kernel above)
         if (keep1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
     };
     int s_tap = 0, s_c0 = c_first;
-    Ctl cur;
+    ConvCtl cur;
     auto tap_body = [&](auto cur_tag, auto nxt_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(cur_tag)::value, N = decltype(nxt_tag)::value;
         if (cur.w_soff >= 0) load_w(cur.w_stage, cur.w_soff);
         int tap1 = s_tap + 1, c01 = s_c0;
         if (tap1 == 27) { tap1 = 0; c01 += 32; }
-        Ctl nxt;
+        ConvCtl nxt;
         uint32_t hfin;
         u32x2 cw;
-        const char* ws = wst + cur.n_stage * W_BYTES;
+        const char* ws = wst + cur.n_stage * G::W_BYTES;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
 #pragma unroll
@@ -681,12 +552,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
             if (j == 5) {
                 int d0 = __builtin_amdgcn_readfirstlane((int)cw[0]), d1 = __builtin_amdgcn_readfirstlane((int)cw[1]);
                 asm volatile("" : "+s"(d0), "+s"(d1), "+s"(c01));
-                nxt = unpack_ctl((uint32_t)d0, (uint32_t)d1, c01);
+                nxt = conv_unpack_ctl<G>((uint32_t)d0, (uint32_t)d1, c01, c_end);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        read_hoff(cur.n_q);
-        read_ctl(tap1 == 26 ? 0 : tap1 + 1);
+        conv_read_hoff<G>(hoff_nx, rowtab_lds, cur.n_q);
+        conv_read_ctl(cw_nx, ctltab_lds, tap1 == 26 ? 0 : tap1 + 1);
         if (cur.h_q >= 0) blds16(x_rsrc, halo + cur.h_q * 1024, hfin, cur.h_soff);
         sync_all(cur.h_q >= 0);
         cur = nxt;
@@ -703,7 +574,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
     if ((blockIdx.x >> 8) & 1) __builtin_amdgcn_s_setprio(1);
     __syncthreads();                                             // the tables are complete
 #pragma unroll
-    for (int k = 0; k < Q_PLANE1 / 4; ++k) {
+    for (int k = 0; k < G::Q_PLANE1 / 4; ++k) {
         const int q = wave + 4 * k;
         blds16(x_rsrc, halo + q * 1024, rowtab[q * 16 + (lane >> 2)] + hslot, c_first * 2);
     }
@@ -715,10 +586,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
     for (int i = 0; i < 4; ++i) af[0][i] = *(const bf16x8*)a_addr(i, 0);
 #pragma unroll
     for (int j = 0; j < 8; ++j) bfr[j] = *(const bf16x8*)(wst + b_off0 + j * 1024);
-    cur = unpack_ctl((uint32_t)__builtin_amdgcn_readfirstlane((int)ctltab[wave * 54]),
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)ctltab[wave * 54 + 1]), c_first);
-    read_hoff(wave + 24);                                        // tap 0's piece slot: wave + 4 * 6
-    read_ctl(1);
+    cur = conv_unpack_ctl<G>((uint32_t)__builtin_amdgcn_readfirstlane((int)ctltab[wave * 54]),
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)ctltab[wave * 54 + 1]), c_first, c_end);
+    conv_read_hoff<G>(hoff_nx, rowtab_lds, wave + 24);                                        // tap 0's piece slot: wave + 4 * 6
+    conv_read_ctl(cw_nx, ctltab_lds, 1);
     {
         const int total = 27 * nchunks;
         for (int g = 0; g + 1 < total; g += 2) {
@@ -869,9 +740,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e] * rstd_i[i] * (1.0f + sc[e]) + sh[e]);
                         }
-                        u32x2 o;
-                        o[0] = pack_bf16(v[0], v[1]);
-                        o[1] = pack_bf16(v[2], v[3]);
+                        const u32x2 o = pack_bf16x4(v);
                         const int chunk = j * 2 + (lane >> 5);
                         *(u32x2*)(scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4) + ((lane >> 4) & 1) * 8) = o;
                     }
@@ -1049,110 +918,7 @@ extern "C" int ltxmi_debug_set_conv_stamps(void* buf) {
 #endif
 namespace ltxmi {
 
-// the shapes the direct convolution takes at all (either form)
-static bool conv3d_direct_takes(const ltxmi_conv3d_args* a) {
-    const int st = a->stride_t > 0 ? a->stride_t : 1, sh = a->stride_hw > 0 ? a->stride_hw : 1;
-    const int kt = a->kernel_t > 0 ? a->kernel_t : 3;
-    if (st != 1 || sh != 1 || kt != 3 || a->out_T > 0 || a->tpad > 0) return false;
-    if (a->Cin % 64 != 0 || a->Cout % 8 != 0 || !a->bias) return false;
-    if ((int64_t)a->B * a->T * a->H * a->W * a->Cin * 2 >= 0x7ffffff0ll) return false;   // halo rows are addressed with 32-bit byte offsets
-    if (a->d2s && (a->Cout % 1024 != 0 || a->add)) return false;       // a 128-column block must be one (p1 p2 p3)
-    // the residual's channel wrap (c' mod Cres/8) is a mask in the four-wave form
-    if (a->d2s && a->residual && (a->res_channels < 8 || ((a->res_channels >> 3) & ((a->res_channels >> 3) - 1)) != 0)) return false;
-    return true;
-}
-// whole 128-channel blocks: the four-wave form, two workgroups per CU (algo 3 asks for it, algo 4 for the eight-wave form)
-// (from 768 workgroups = 1.5 rounds of the chip's 512 slots; measured: 896 workgroups +5.8 %, 600 -0.6 %, 224 -21 %)
-static bool conv3d_direct_four_wave_form(const ltxmi_conv3d_args* a, int64_t grid) {
-    return a->Cout % 128 == 0 && grid < (1ll << 31) && ((a->algo != 4 && grid >= 768) || a->algo == 3);
-}
-
-// How a call is laid out on the chip.  Tiles are 2 (t) x 8 x 16 positions; the 16-position direction is W, or H (swap: the
-// four-wave form only).  ksplit > 1: the input channels in ksplit ranges with fp32 partial sums and a finalising pass -- for the
-// wide, short layers (Cin >= 1024: the partial sums are Cin / (4 ksplit) times smaller than the halo traffic they replace) whose
-// tiles do not fill the chip: 1024 -> 1024 at 13 x 16 x 24 positions is 224 tiles of which 70 % of the positions exist (W = 24
-// is 1.5 tiles); swapped it is 168 tiles at 93 %, and three channel ranges make 504 workgroups for the 512 slots.
-static ConvPlan conv3d_plan(const ltxmi_conv3d_args* a) {      // a != NULL, sizes positive; algo honoured as given
-    ConvPlan pl = {};
-    // output grid: nn.Conv3d arithmetic on the padded input (time padded by tpad frames in front, and by one replicated frame
-    // behind when not causal; space padded by 1): floor((L + pad - 3) / s) + 1
-    pl.sT = a->stride_t > 0 ? a->stride_t : 1; pl.sHW = a->stride_hw > 0 ? a->stride_hw : 1;
-    pl.kt = a->kernel_t > 0 ? a->kernel_t : 3;       // 1: a 3x3 nn.Conv2d applied to every frame
-    pl.tpad = pl.kt == 1 ? 0 : (a->tpad > 0 ? a->tpad : (a->causal ? 2 : 1));
-    const int tpad_back = (pl.kt == 1 || a->tpad > 0 || a->causal) ? 0 : 1;
-    pl.oT = a->out_T > 0 ? a->out_T : (a->T + pl.tpad + tpad_back - pl.kt) / pl.sT + 1;
-    pl.oH = (a->H + 2 - 3) / pl.sHW + 1; pl.oW = (a->W + 2 - 3) / pl.sHW + 1;
-    pl.M = (int64_t)a->B * pl.oT * pl.oH * pl.oW;
-    pl.epi = a->d2s ? 2 : (a->add ? 1 : 0);
-    pl.ksplit = 1;
-    const ConvRoute gemm = conv3d_gemm_tile(pl.M, a->Cout) == 256 ? CONV_GEMM256 : CONV_GEMM128;
-    if (a->algo == 1 || !conv3d_direct_takes(a)) {
-        pl.route = a->algo >= 2 ? CONV_REFUSED : gemm;
-        return pl;
-    }
-    pl.tiles_t = (a->T + CD_TT - 1) / CD_TT; pl.tiles_n = (a->Cout + 127) / 128;
-    const int64_t per = (int64_t)a->B * pl.tiles_t * pl.tiles_n;
-    const int64_t g_n = per * ((a->H + 7) / 8) * ((a->W + 15) / 16), g_s = per * ((a->W + 7) / 8) * ((a->H + 15) / 16);
-    bool four_wave = conv3d_direct_four_wave_form(a, g_n);
-    const double positions = (double)a->B * pl.tiles_t * CD_TT * a->H * a->W * pl.tiles_n;       // (x 128 channels each, t rounded up)
-    auto eff4 = [&](int64_t g, int S) {           // useful share of the tiles x fill of the last round of 512 slots - the split's price
-        const double rounds = (double)g * S / 512.0;
-        return positions / ((double)g * 256.0) * rounds / (double)(int64_t)(rounds + 0.999999) - 0.03 * (S - 1);
-    };
-    const double eff_now = four_wave ? eff4(g_n, 1)
-                                     : positions / ((double)g_n * 256.0) * ((double)g_n / 256.0) / (double)((g_n + 255) / 256) * 0.93;
-    // The channel split: the product's own choice (algo 0 / 2 / 3), output rows the finalising pass takes (512 or n x 1024
-    // channels).  Cin >= 1024: wherever it buys more than 5 % of the launch at 3 % per extra range.  512 <= Cin < 1024 (the partial
-    // sums cost twice as much per FLOP): two ranges only, and only for a call that asks for a norm the unsplit form could not
-    // fuse -- the finalising pass replaces that launch (0.084 ms beside a 0.55-ms convolution at the decoder's 512-channel stage,
-    // whose 624 workgroups are 2.44 rounds of the eight-wave form), which the efficiency figure does not see.
-    const int nch = a->Cin / 32;
-    const bool rows_ok = (a->Cout == 512 || a->Cout % 1024 == 0) && a->Cout <= 4096;
-    const bool wants_unfusable_norm = a->post_norm && !(a->Cout == 128 || (a->d2s && a->Cout == 1024));
-    if (rows_ok && a->Cin % 32 == 0 && a->algo != 1 && a->algo != 4 && (a->Cin >= 1024 || (a->Cin >= 512 && wants_unfusable_norm))) {
-        const int64_t g = g_s < g_n ? g_s : g_n;
-        const bool wide = a->Cin >= 1024;
-        const double price = wide ? 0.03 : 0.06;
-        int best = 1;
-        double best_eff = wide ? eff_now + 0.05 : eff_now - 0.05;
-        for (int S = 2; S <= (wide ? 4 : 2) && S * 4 <= nch; ++S) {
-            const double e = eff4(g, S) + 0.03 * (S - 1) - price * (S - 1);
-            if (g * S < (1ll << 31) && e > best_eff) { best = S; best_eff = e; }
-        }
-        if (best > 1) {
-            pl.split_bytes = (int64_t)best * a->B * a->T * a->H * a->W * a->Cout * 4;
-            if (a->workspace && a->workspace_bytes >= pl.split_bytes && (((uintptr_t)a->workspace) & 15) == 0) {
-                pl.ksplit = best; four_wave = true; pl.swap = g_s < g_n;
-            }
-        }
-    }
-    if (pl.ksplit == 1 && four_wave && (g_s + 511) / 512 < (g_n + 511) / 512) pl.swap = 1;    // fewer rounds of the chip
-    pl.tiles_8 = pl.swap ? (a->W + 7) / 8 : (a->H + 7) / 8;
-    pl.tiles_16 = pl.swap ? (a->H + 15) / 16 : (a->W + 15) / 16;
-    pl.grid = per * pl.tiles_8 * pl.tiles_16;
-    // post_norm rides along where a wave holds every channel of its output positions: ONE 128-channel block of the four-wave
-    // form (plain store; with `add` only as the second output y_norm beside the raw y), or its depth-to-space store to 128
-    // channels (second output only: a 128-column block is one (p1 p2 p3)) -- and on every call split over its input channels
-    // (the finalising pass holds whole rows).  Without y_norm the activated result is the only output: the plain store only.
-    if (a->y_norm || !(a->add || a->d2s)) {
-        pl.fuses_post_norm = pl.ksplit > 1 ||
-                             (four_wave && (a->y_norm ? (a->d2s && a->Cout == 1024) || (!a->d2s && a->add && a->Cout == 128)
-                                                      : a->Cout == 128));
-    }
-    if (four_wave) {
-        pl.route = CONV_DIRECT4;
-        pl.epi = pl.ksplit > 1 ? 6 : pl.epi + (a->post_norm && pl.fuses_post_norm ? 3 : 0);
-    } else if (pl.grid >= (1ll << 31) || (pl.grid < 128 && a->algo < 2)) {
-        // one eight-wave workgroup per CU is resident: below ~half the CUs the implicit GEMM's smaller tiles fill the chip
-        // better (algo >= 2 asks for the direct convolution whatever the grid)
-        pl.route = a->algo >= 2 ? CONV_REFUSED : gemm;
-    } else {
-        pl.route = CONV_DIRECT8;
-    }
-    return pl;
-}
-
-static int launch_conv3d_direct(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream) {
+int launch_conv3d_direct(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream) {
     ConvDirectP p;
     p.x = (const uint16_t*)a->x; p.w = (const uint16_t*)a->w; p.bias = (const uint16_t*)a->bias;
     p.y = (uint16_t*)a->y; p.add = (const uint16_t*)a->add;
@@ -1164,140 +930,39 @@ static int launch_conv3d_direct(const ltxmi_conv3d_args* a, const ConvPlan& pl, 
     const int64_t grid = pl.grid * pl.ksplit;
     p.post_scale = a->post_scale; p.post_shift = a->post_shift; p.post_eps = a->post_eps;
     p.y2 = (uint16_t*)a->y_norm;
-    if (pl.route == CONV_DIRECT4) {
-#define LTXMI_CDV3_LAUNCH(E)                                                                                   \
-        {                                                                                                      \
-            static unsigned long long lds_done = 0;                                                            \
-            if (const int rc_ = reserve_lds((const void*)v3::conv3d_direct_v3_kernel<E>, v3::SMEM, &lds_done,  \
-                                            "ltxmi_conv3d_ndhwc_bf16"))                                        \
-                return rc_;                                                                                    \
-            hipLaunchKernelGGL(v3::conv3d_direct_v3_kernel<E>, dim3((unsigned)grid), dim3(256), v3::SMEM,      \
-                               stream, p);                                                                     \
-        }
-        if (pl.epi == 6) {                  // the channel split, then the finalising pass
-            LTXMI_CDV3_LAUNCH(6)
-            if (const int rc_ = check_launch("ltxmi_conv3d_ndhwc_bf16")) return rc_;
-            ConvFinalizeP f;
-            f.part = (const float*)a->workspace; f.ksplit = pl.ksplit; f.rows = (int64_t)a->B * a->T * a->H * a->W;
-            f.bias = p.bias; f.add = p.add; f.res = p.res; f.res_ch = p.res_ch;
-            // post_norm without y_norm: the activated result is the only output (to y); with y_norm: raw to y, activated to y_norm
-            f.y = (a->post_norm && !a->y_norm) ? nullptr : p.y;
-            f.y2 = a->post_norm ? (a->y_norm ? (uint16_t*)a->y_norm : p.y) : nullptr;
-            f.B = a->B; f.T = a->T; f.H = a->H; f.W = a->W; f.Cout = a->Cout; f.d2s = a->d2s;
-            f.post_scale = a->post_scale; f.post_shift = a->post_shift; f.post_eps = a->post_eps; f.post_norm = a->post_norm;
-            const dim3 fg((unsigned)f.rows);
-            switch (a->Cout / 256) {
-                case 2: hipLaunchKernelGGL((conv_split_finalize_kernel<4, 128>), fg, dim3(128), 0, stream, f); break;
-                case 4: hipLaunchKernelGGL(conv_split_finalize_kernel<4>, fg, dim3(256), 0, stream, f); break;
-                case 8: hipLaunchKernelGGL(conv_split_finalize_kernel<8>, fg, dim3(256), 0, stream, f); break;
-                case 12: hipLaunchKernelGGL(conv_split_finalize_kernel<12>, fg, dim3(256), 0, stream, f); break;
-                default: hipLaunchKernelGGL(conv_split_finalize_kernel<16>, fg, dim3(256), 0, stream, f); break;
-            }
-            return check_launch("ltxmi_conv3d_ndhwc_bf16");
-        }
-        switch (pl.epi) {
-            case 0: LTXMI_CDV3_LAUNCH(0) break;
-            case 1: LTXMI_CDV3_LAUNCH(1) break;
-            case 2: LTXMI_CDV3_LAUNCH(2) break;
-            case 3: LTXMI_CDV3_LAUNCH(3) break;
-            case 4: LTXMI_CDV3_LAUNCH(4) break;
-            default: LTXMI_CDV3_LAUNCH(5) break;
-        }
-#undef LTXMI_CDV3_LAUNCH
-        return check_launch("ltxmi_conv3d_ndhwc_bf16");
+    const char* what = "ltxmi_conv3d_ndhwc_bf16";
+    const dim3 g((unsigned)grid);
+    auto go8 = [&](auto e) { return launch_with_lds<conv3d_direct_kernel<decltype(e)::value>>(p, g, dim3(512), ConvGeo8::SMEM, stream, what); };
+    auto go4 = [&](auto e) { return launch_with_lds<v3::conv3d_direct_v3_kernel<decltype(e)::value>>(p, g, dim3(256), ConvGeo4::SMEM, stream, what); };
+    if (pl.route == CONV_DIRECT8) return pl.epi == 2 ? go8(epi_t<2>{}) : pl.epi == 1 ? go8(epi_t<1>{}) : go8(epi_t<0>{});
+    switch (pl.epi) {
+        case 0: return go4(epi_t<0>{});
+        case 1: return go4(epi_t<1>{});
+        case 2: return go4(epi_t<2>{});
+        case 3: return go4(epi_t<3>{});
+        case 4: return go4(epi_t<4>{});
+        case 5: return go4(epi_t<5>{});
+        default: break;
     }
-#define LTXMI_CD_LAUNCH(E)                                                                                     \
-    {                                                                                                          \
-        static unsigned long long lds_done = 0;                                                                \
-        if (const int rc_ = reserve_lds((const void*)conv3d_direct_kernel<E>, CD_SMEM, &lds_done,              \
-                                        "ltxmi_conv3d_ndhwc_bf16"))                                            \
-            return rc_;                                                                                        \
-        hipLaunchKernelGGL(conv3d_direct_kernel<E>, dim3((unsigned)grid), dim3(512), CD_SMEM, stream, p);      \
+    // epi 6: the channel split, then the finalising pass
+    if (const int rc = go4(epi_t<6>{})) return rc;
+    ConvFinalizeP f;
+    f.part = (const float*)a->workspace; f.ksplit = pl.ksplit; f.rows = (int64_t)a->B * a->T * a->H * a->W;
+    f.bias = p.bias; f.add = p.add; f.res = p.res; f.res_ch = p.res_ch;
+    // post_norm without y_norm: the activated result is the only output (to y); with y_norm: raw to y, activated to y_norm
+    f.y = (a->post_norm && !a->y_norm) ? nullptr : p.y;
+    f.y2 = a->post_norm ? (a->y_norm ? (uint16_t*)a->y_norm : p.y) : nullptr;
+    f.B = a->B; f.T = a->T; f.H = a->H; f.W = a->W; f.Cout = a->Cout; f.d2s = a->d2s;
+    f.post_scale = a->post_scale; f.post_shift = a->post_shift; f.post_eps = a->post_eps; f.post_norm = a->post_norm;
+    const dim3 fg((unsigned)f.rows);
+    switch (a->Cout / 256) {
+        case 2: hipLaunchKernelGGL((conv_split_finalize_kernel<4, 128>), fg, dim3(128), 0, stream, f); break;
+        case 4: hipLaunchKernelGGL(conv_split_finalize_kernel<4>, fg, dim3(256), 0, stream, f); break;
+        case 8: hipLaunchKernelGGL(conv_split_finalize_kernel<8>, fg, dim3(256), 0, stream, f); break;
+        case 12: hipLaunchKernelGGL(conv_split_finalize_kernel<12>, fg, dim3(256), 0, stream, f); break;
+        default: hipLaunchKernelGGL(conv_split_finalize_kernel<16>, fg, dim3(256), 0, stream, f); break;
     }
-    if (pl.epi == 2) LTXMI_CD_LAUNCH(2)
-    else if (pl.epi == 1) LTXMI_CD_LAUNCH(1)
-    else LTXMI_CD_LAUNCH(0)
-#undef LTXMI_CD_LAUNCH
-    return check_launch("ltxmi_conv3d_ndhwc_bf16");
+    return check_launch(what);
 }
 
 }  // namespace ltxmi
-
-using namespace ltxmi;
-
-// the two queries: fields of the plan of the arguments as given (0 without a bias -- the direct convolution needs one)
-static bool conv3d_plannable(const ltxmi_conv3d_args* a) {
-    return a != nullptr && a->bias != nullptr && a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0;
-}
-extern "C" int ltxmi_conv3d_fuses_post_norm(const ltxmi_conv3d_args* a) { return conv3d_plannable(a) && conv3d_plan(a).fuses_post_norm; }
-extern "C" int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* a) { return conv3d_plannable(a) ? conv3d_plan(a).split_bytes : 0; }
-
-// The ONE place that validates a convolution call and plans it: ltxmi_conv3d_ndhwc_bf16 launches what this leaves in *pl and
-// ltxmi_conv3d_route reports it.  Pure host arithmetic on the struct: no device call, no device memory read.  Returns LTXMI_OK
-// with the plan in *pl, or the negative ltxmi_status (error text set).
-static int conv3d_check(const ltxmi_conv3d_args* a, ConvPlan* plan) {
-    LTXMI_REQUIRE(a && a->x && a->w && a->y, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: NULL argument");
-    LTXMI_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, LTXMI_ERR_INVALID_ARG,
-                  "ltxmi_conv3d_ndhwc_bf16: non-positive shape");
-    const ConvPlan pl = *plan = conv3d_plan(a);
-    LTXMI_REQUIRE(a->Cin % 64 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cin=%d must be a multiple of 64", a->Cin);
-    LTXMI_REQUIRE(a->Cout % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cout=%d must be a multiple of 8", a->Cout);
-    LTXMI_REQUIRE((pl.sT == 1 || pl.sT == 2) && (pl.sHW == 1 || pl.sHW == 2), LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: strides must be 1 or 2");
-    LTXMI_REQUIRE(pl.kt == 3 || (pl.kt == 1 && pl.sT == 1 && a->tpad == 0 && a->out_T == 0), LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: kernel_t must be 3, or 1 without time stride/padding");
-    LTXMI_REQUIRE(!(a->d2s && (pl.sT != 1 || pl.sHW != 1 || pl.oT != a->T)), LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: depth-to-space store needs a stride-1, same-size convolution");
-    LTXMI_REQUIRE(pl.M < (1ll << 31) && (int64_t)a->B * (2 * a->T) * (2 * a->H) * (2 * a->W) < (1ll << 31),
-                  LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: too many positions");
-    if (a->d2s) {
-        LTXMI_REQUIRE(a->Cout % 32 == 0, LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: depth-to-space needs Cout %% 32 == 0 (got %d)", a->Cout);
-        if (a->residual)
-            LTXMI_REQUIRE(a->res_channels > 0 && a->res_channels % 8 == 0, LTXMI_ERR_INVALID_ARG,
-                          "ltxmi_conv3d_ndhwc_bf16: bad residual channel count %d", a->res_channels);
-    }
-    LTXMI_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->w) & 15) == 0 && (((uintptr_t)a->y | (uintptr_t)a->bias) & 7) == 0,
-                  LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: misaligned pointer");
-    LTXMI_REQUIRE(a->algo >= 0 && a->algo <= 4, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: algo %d not in {0 .. 4}", a->algo);
-    LTXMI_REQUIRE(a->workspace_bytes >= 0 && (a->workspace != nullptr || a->workspace_bytes == 0), LTXMI_ERR_INVALID_ARG,
-                  "ltxmi_conv3d_ndhwc_bf16: workspace_bytes without a workspace");
-    if (a->post_norm) {
-        LTXMI_REQUIRE(a->post_norm == 1 && (a->post_scale != nullptr) == (a->post_shift != nullptr) && a->post_eps >= 0.f,
-                      LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: post_norm must be 0 or 1, post_scale / post_shift both given or both NULL");
-        LTXMI_REQUIRE((((uintptr_t)a->post_scale | (uintptr_t)a->post_shift) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: misaligned post_scale / post_shift");
-        LTXMI_REQUIRE(((uintptr_t)a->y_norm & 15) == 0 && a->y_norm != a->y, LTXMI_ERR_INVALID_ARG,
-                      "ltxmi_conv3d_ndhwc_bf16: y_norm must be 16-byte aligned and distinct from y");
-        LTXMI_REQUIRE(pl.fuses_post_norm, LTXMI_ERR_UNSUPPORTED,
-                      "ltxmi_conv3d_ndhwc_bf16: post_norm is applied by the four-wave direct convolution where a wave holds all "
-                      "channels of a position (ask ltxmi_conv3d_fuses_post_norm first)");
-    } else {
-        LTXMI_REQUIRE(a->y_norm == nullptr, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: y_norm without post_norm");
-    }
-    LTXMI_REQUIRE(pl.route != CONV_REFUSED, LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_conv3d_ndhwc_bf16: algo = %d (direct convolution) does not take this shape", a->algo);
-    // (`d2s` with `add` never reaches the direct forms: conv3d_direct_takes)
-    LTXMI_REQUIRE(!(a->d2s && a->add), LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: `add` is for the plain store only");
-    return LTXMI_OK;
-}
-
-extern "C" int ltxmi_conv3d_route(const ltxmi_conv3d_args* a, ltxmi_conv3d_route_info* out) {
-    LTXMI_REQUIRE(out != nullptr, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_route: NULL out");
-    *out = ltxmi_conv3d_route_info{-1, 0, 0, 0, 0};
-    ConvPlan pl;
-    if (const int rc = conv3d_check(a, &pl)) return rc;
-    out->route = (int32_t)pl.route;               // CONV_GEMM128 .. CONV_DIRECT4 are 0 .. 3, the header's numbering
-    out->epilogue = pl.epi;
-    out->ksplit = pl.ksplit;
-    out->swap_hw = pl.swap;
-    out->finalize_blocks = pl.ksplit > 1 ? a->Cout / 256 : 0;
-    return LTXMI_OK;
-}
-
-extern "C" int ltxmi_conv3d_ndhwc_bf16(const ltxmi_conv3d_args* a, void* stream) {
-    ConvPlan pl;
-    if (const int rc = conv3d_check(a, &pl)) return rc;
-    if (pl.route == CONV_DIRECT4 || pl.route == CONV_DIRECT8) return launch_conv3d_direct(a, pl, (hipStream_t)stream);
-    return launch_conv3d_gemm(a, pl, (hipStream_t)stream);
-}

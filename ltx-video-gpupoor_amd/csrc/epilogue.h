@@ -1,0 +1,33 @@
+// epilogue.h -- the pieces the epilogues of gemm.hip and conv_direct.hip have in common (force-inlined device helpers).
+#pragma once
+#include "common.h"
+
+namespace ltxmi {
+
+// ---- four accumulator values (a float[4], an f32x4, a pointer to four floats) and four packed bf16 operands (8 bytes)
+template <class V>
+__device__ __forceinline__ void add_bf16x4(V&& v, u32x2 w) {
+    v[0] += bf_lo(w[0]); v[1] += bf_hi(w[0]);
+    v[2] += bf_lo(w[1]); v[3] += bf_hi(w[1]);
+}
+template <class V>
+__device__ __forceinline__ void mul_sum_bf16x4(V&& v, u32x2 a, u32x2 b) {      // v *= a + b
+    v[0] *= bf_lo(a[0]) + bf_lo(b[0]); v[1] *= bf_hi(a[0]) + bf_hi(b[0]);
+    v[2] *= bf_lo(a[1]) + bf_lo(b[1]); v[3] *= bf_hi(a[1]) + bf_hi(b[1]);
+}
+template <class V>
+__device__ __forceinline__ u32x2 pack_bf16x4(V&& v) {
+    return u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+}
+// ---- a wave's 4-KB LDS scratch: 32 rows x 128 B (64 bf16 columns), 16-byte chunks XOR-swizzled by row & 7; written in the
+// accumulators' layout and read row-major, or the other way round.  Both return the ADDRESS, formed term by term: hipcc folds the
+// row term's constant part into the instruction's offset field only then.  The 8-byte piece of fragment column j in row row_l:
+__device__ __forceinline__ char* scratch_acc_ptr(char* scr, int row_l, int j, int lane) {
+    const int chunk = j * 2 + (lane >> 5);
+    return scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4) + ((lane >> 4) & 1) * 8;
+}
+__device__ __forceinline__ char* scratch_row_ptr(char* scr, int row_l, int chunk) {      // row-major: 16-byte piece `chunk` of row row_l
+    return scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4);
+}
+
+}  // namespace ltxmi

@@ -23,11 +23,8 @@
 //
 // Block -> tile mapping is XCD-aware: the 8 XCDs each get a contiguous band of M-tiles so
 // the W panel and the A rows they share stay in that XCD's private L2.
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "common.h"
+#include "conv.h"
+#include "epilogue.h"
 
 namespace ltxmi {
 
@@ -312,8 +309,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(Gem
         for (int j = 0; j < NI; ++j) {
             const int n = n0 + wn * WN + j * 16 + ecol;
             float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            v[0] += bf_lo(bias_v[j][0]); v[1] += bf_hi(bias_v[j][0]);
-            v[2] += bf_lo(bias_v[j][1]); v[3] += bf_hi(bias_v[j][1]);
+            add_bf16x4(v, bias_v[j]);
             if (EPI == LTXMI_EPI_GELU_TANH) {
                 // the packed form of the persistent kernel: every GEMM kernel produces the same bits for a given row
                 // (the accumulation order over K is the same in all of them), whatever M made the dispatcher choose
@@ -324,14 +320,10 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(Gem
                 for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
             }
             if (GATED) {
-                v[0] *= bf_lo(gt_v[j][0]) + bf_lo(ge_v[j][0]);
-                v[1] *= bf_hi(gt_v[j][0]) + bf_hi(ge_v[j][0]);
-                v[2] *= bf_lo(gt_v[j][1]) + bf_lo(ge_v[j][1]);
-                v[3] *= bf_hi(gt_v[j][1]) + bf_hi(ge_v[j][1]);
+                mul_sum_bf16x4(v, gt_v[j], ge_v[j]);
             }
             if (RESID) {
-                v[0] += bf_lo(rr_v[j][0]); v[1] += bf_hi(rr_v[j][0]);
-                v[2] += bf_lo(rr_v[j][1]); v[3] += bf_hi(rr_v[j][1]);
+                add_bf16x4(v, rr_v[j]);
             }
             if (!(m_ok && n < p.N)) continue;
             u32x2 o;
@@ -351,14 +343,12 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(Gem
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] += bf2f(rrow[((cp + e) % cm) * 8]);
                 }
-                o[0] = pack_bf16(v[0], v[1]);
-                o[1] = pack_bf16(v[2], v[3]);
+                o = pack_bf16x4(v);
                 const int64_t opos = (((int64_t)b_ * (2 * p.cT - 1) + to) * (2 * p.cH) + yo) * (2 * p.cW) + xo;
                 *(u32x2*)(p.C + opos * Cp + cp) = o;
                 continue;
             }
-            o[0] = pack_bf16(v[0], v[1]);
-            o[1] = pack_bf16(v[2], v[3]);
+            o = pack_bf16x4(v);
             *(u32x2*)(p.C + (int64_t)m * p.ldc + n) = o;
             if (EPI == EPI_SUMSQ)
                 ss[j / 4] = sumsq4(ss[j / 4], o);
@@ -571,15 +561,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_persistent
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int row_l = t * 8 + (lane >> 3), chunk = lane & 7;
-                    *(u32x4*)(scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4)) = rres[t];
+                    *(u32x4*)scratch_row_ptr(scr, row_l, chunk) = rres[t];
                 }
                 if (c + 1 < MI / 2) load_res(m0, n0, c + 1);
 #pragma unroll
                 for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
                     for (int j = 0; j < NE; ++j) {
-                        const int row_l = ii * 16 + erow, chunk = j * 2 + (lane >> 5);
-                        rr_c[ii][j] = *(const u32x2*)(scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4) + ((lane >> 4) & 1) * 8);
+                        rr_c[ii][j] = *(const u32x2*)scratch_acc_ptr(scr, ii * 16 + erow, j, lane);
                     }
             }
 #pragma unroll
@@ -610,10 +599,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_persistent
                         for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
                     }
                     if (GATED) {
-                        v[0] *= bf_lo(gt_v[j][0]) + bf_lo(ge_v[j][0]);
-                        v[1] *= bf_hi(gt_v[j][0]) + bf_hi(ge_v[j][0]);
-                        v[2] *= bf_lo(gt_v[j][1]) + bf_lo(ge_v[j][1]);
-                        v[3] *= bf_hi(gt_v[j][1]) + bf_hi(ge_v[j][1]);
+                        mul_sum_bf16x4(v, gt_v[j], ge_v[j]);
                     }
                     if (RESID) {
                         v[0] += bf_lo(rr_v[j][0]); v[1] += bf_hi(rr_v[j][0]);
@@ -625,8 +611,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_persistent
                     if (EPI == EPI_SUMSQ)
                         ss = sumsq4(ss, o);
                     // 8-byte piece (j*4 + lane>>4) of scratch row row_l; 16-byte chunks XOR-swizzled by row
-                    const int chunk = j * 2 + (lane >> 5);
-                    *(u32x2*)(scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4) + ((lane >> 4) & 1) * 8) = o;
+                    *(u32x2*)scratch_acc_ptr(scr, row_l, j, lane) = o;
                 }
                 if (EPI == EPI_SUMSQ) {
                     // these 64 columns of row m: lanes l, l+16, l+32, l+48 hold its four 16-column pieces
@@ -641,7 +626,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_persistent
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int row_l = t * 8 + (lane >> 3), chunk = lane & 7;
-                const u32x4 w = *(const u32x4*)(scr + row_l * 128 + ((chunk ^ (row_l & 7)) << 4));
+                const u32x4 w = *(const u32x4*)scratch_row_ptr(scr, row_l, chunk);
                 const int m = m0 + wm * WM + c * 32 + row_l;
                 const int n = nh0 + chunk * 8;
                 const uint32_t off = (m < p.M && n < p.N) ? (uint32_t)(((int64_t)m * p.ldc + n) * 2) : 0xfffffff0u;
@@ -867,30 +852,25 @@ static int launch_tile(const GemmParams& p0, int epi, hipStream_t stream, const 
     const int grid = p.tiles_m * p.tiles_n;
     constexpr int threads = WAVES_M * WAVES_N * 64;
     constexpr int smem = 2 * (BM + BN) * BK * 2;
-#define LTXMI_GEMM_LAUNCH(E)                                                                          \
-    {                                                                                                 \
-        auto kern = gemm_bf16_nt_kernel<BM, BN, WAVES_M, WAVES_N, E, MODE>;                                \
-        static unsigned long long lds_done = 0;                                                       \
-        if (const int rc_ = reserve_lds((const void*)kern, smem, &lds_done, what)) return rc_;        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), smem, stream, p);                        \
-    }
+    auto go = [&](auto e) {
+        return launch_with_lds<gemm_bf16_nt_kernel<BM, BN, WAVES_M, WAVES_N, decltype(e)::value, MODE>>(p, dim3(grid), dim3(threads), smem,
+                                                                                                    stream, what);
+    };
     if constexpr (MODE == 0) {
         switch (epi) {
-            case LTXMI_EPI_NONE: LTXMI_GEMM_LAUNCH(LTXMI_EPI_NONE) break;
-            case EPI_SUMSQ: LTXMI_GEMM_LAUNCH(EPI_SUMSQ) break;
-            case LTXMI_EPI_GELU_TANH: LTXMI_GEMM_LAUNCH(LTXMI_EPI_GELU_TANH) break;
-            case LTXMI_EPI_SILU: LTXMI_GEMM_LAUNCH(LTXMI_EPI_SILU) break;
-            case LTXMI_EPI_GATE_RESIDUAL: LTXMI_GEMM_LAUNCH(LTXMI_EPI_GATE_RESIDUAL) break;
-            case EPI_RESIDUAL: LTXMI_GEMM_LAUNCH(EPI_RESIDUAL) break;
+            case LTXMI_EPI_NONE: return go(epi_t<LTXMI_EPI_NONE>{});
+            case EPI_SUMSQ: return go(epi_t<EPI_SUMSQ>{});
+            case LTXMI_EPI_GELU_TANH: return go(epi_t<LTXMI_EPI_GELU_TANH>{});
+            case LTXMI_EPI_SILU: return go(epi_t<LTXMI_EPI_SILU>{});
+            case LTXMI_EPI_GATE_RESIDUAL: return go(epi_t<LTXMI_EPI_GATE_RESIDUAL>{});
+            case EPI_RESIDUAL: return go(epi_t<EPI_RESIDUAL>{});
             default: set_error("%s: bad epilogue %d", what, epi); return LTXMI_ERR_INVALID_ARG;
         }
     } else {
-        if (epi == EPI_D2S) LTXMI_GEMM_LAUNCH(EPI_D2S)
-        else if (epi == EPI_RESIDUAL) LTXMI_GEMM_LAUNCH(EPI_RESIDUAL)
-        else LTXMI_GEMM_LAUNCH(LTXMI_EPI_NONE)
+        if (epi == EPI_D2S) return go(epi_t<EPI_D2S>{});
+        if (epi == EPI_RESIDUAL) return go(epi_t<EPI_RESIDUAL>{});
+        return go(epi_t<LTXMI_EPI_NONE>{});
     }
-#undef LTXMI_GEMM_LAUNCH
-    return check_launch(what);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
@@ -904,27 +884,22 @@ static int launch_persistent(const GemmParams& p0, int epi, hipStream_t stream, 
     const int grid = ntiles < n_cu ? ntiles : n_cu;      // one 8-wave workgroup per CU (all 160 KB of LDS)
     constexpr int threads = WAVES_M * WAVES_N * 64;
     constexpr int smem = 2 * (BM + BN) * BK * 2 + WAVES_M * WAVES_N * 4096;   // 2 stages + epilogue scratch
-#define LTXMI_GEMM_LAUNCH_P(E)                                                                        \
-    {                                                                                                 \
-        auto kern = gemm_bf16_nt_persistent_kernel<BM, BN, WAVES_M, WAVES_N, E>;                      \
-        static unsigned long long lds_done = 0;                                                       \
-        if (const int rc_ = reserve_lds((const void*)kern, smem, &lds_done, what)) return rc_;        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), smem, stream, p);                        \
-    }
+    auto go = [&](auto e) {
+        return launch_with_lds<gemm_bf16_nt_persistent_kernel<BM, BN, WAVES_M, WAVES_N, decltype(e)::value>>(p, dim3(grid), dim3(threads),
+                                                                                                     smem, stream, what);
+    };
     switch (epi) {
         // the plain epilogue runs on the row-sums instance with the sums switched off (sumsq_cols = 0: its extra stores
         // carry an out-of-range offset and are dropped): same bits, and measured 3-6 % faster than a dedicated instance,
         // which hipcc happens to allocate worst of all (55 spilled VGPRs)
         case LTXMI_EPI_NONE:
-        case EPI_SUMSQ: LTXMI_GEMM_LAUNCH_P(EPI_SUMSQ) break;
-        case LTXMI_EPI_GELU_TANH: LTXMI_GEMM_LAUNCH_P(LTXMI_EPI_GELU_TANH) break;
-        case LTXMI_EPI_SILU: LTXMI_GEMM_LAUNCH_P(LTXMI_EPI_SILU) break;
-        case LTXMI_EPI_GATE_RESIDUAL: LTXMI_GEMM_LAUNCH_P(LTXMI_EPI_GATE_RESIDUAL) break;
-        case EPI_RESIDUAL: LTXMI_GEMM_LAUNCH_P(EPI_RESIDUAL) break;
+        case EPI_SUMSQ: return go(epi_t<EPI_SUMSQ>{});
+        case LTXMI_EPI_GELU_TANH: return go(epi_t<LTXMI_EPI_GELU_TANH>{});
+        case LTXMI_EPI_SILU: return go(epi_t<LTXMI_EPI_SILU>{});
+        case LTXMI_EPI_GATE_RESIDUAL: return go(epi_t<LTXMI_EPI_GATE_RESIDUAL>{});
+        case EPI_RESIDUAL: return go(epi_t<EPI_RESIDUAL>{});
         default: set_error("%s: bad epilogue %d", what, epi); return LTXMI_ERR_INVALID_ARG;
     }
-#undef LTXMI_GEMM_LAUNCH_P
-    return check_launch(what);
 }
 
 // device address of the zero page of the CURRENT device (stands in for a missing bias with stride 0); a __device__
@@ -944,6 +919,22 @@ static const uint16_t* zero_page_ptr() {
     return (const uint16_t*)d;
 }
 
+// what the dense call and the convolution have in common: operands, output, shape; everything else of *p stays as the caller's
+// `GemmParams p = {}` left it (the dense call used to set the convolution's grid and strides to 1: they are read under MODE == 1 and
+// EPI_D2S only, which no dense launch instantiates).  A missing bias is the zero page with stride 0.
+static int gemm_params(GemmParams* p, const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
+                       int M, int N, int K, const char* what) {
+    p->A = (const uint16_t*)A; p->lda = lda;
+    p->W = (const uint16_t*)W; p->ldw = ldw;
+    p->bias = bias ? (const uint16_t*)bias : zero_page_ptr();
+    p->bias_stride = bias ? 1 : 0;
+    LTXMI_REQUIRE(p->bias, LTXMI_ERR_LAUNCH, "%s: cannot resolve the zero page", what);
+    p->C = (uint16_t*)C; p->ldc = ldc;
+    p->M = M; p->N = N; p->K = K;
+    p->rows_per_group = 1;
+    return LTXMI_OK;
+}
+
 // the implicit-GEMM convolution: 256 x 256 tiles (8 waves) when they still fill the chip, else 128 x 128
 int conv3d_gemm_tile(int64_t M, int Cout) {
     const long t256 = (long)((M + 255) / 256) * ((Cout + 255) / 256);
@@ -951,17 +942,10 @@ int conv3d_gemm_tile(int64_t M, int Cout) {
 }
 
 int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream) {
-    GemmParams p;
-    p.A = (const uint16_t*)a->x; p.lda = a->Cin;
-    p.W = (const uint16_t*)a->w; p.ldw = 9ll * pl.kt * a->Cin;
-    p.bias = a->bias ? (const uint16_t*)a->bias : zero_page_ptr();
-    p.bias_stride = a->bias ? 1 : 0;
-    LTXMI_REQUIRE(p.bias, LTXMI_ERR_LAUNCH, "ltxmi_conv3d_ndhwc_bf16: cannot resolve the zero page");
-    p.C = (uint16_t*)a->y; p.ldc = a->Cout;
-    p.M = (int)pl.M; p.N = a->Cout; p.K = 9 * pl.kt * a->Cin;
-    p.R = nullptr; p.ldr = 0; p.gate_table = nullptr; p.gate_temb = nullptr; p.gate_ld = 0; p.rows_per_group = 1;
-    p.sumsq = nullptr; p.sumsq_cols = 0; p.sumsq_ld = 0; p.a_kblk = 0; p.a_kblk_stride = 0;
-    p.tiles_m = p.tiles_n = 0;
+    GemmParams p = {};
+    if (const int rc = gemm_params(&p, a->x, a->Cin, a->w, 9ll * pl.kt * a->Cin, a->bias, a->y, a->Cout, (int)pl.M, a->Cout,
+                                   9 * pl.kt * a->Cin, "ltxmi_conv3d_ndhwc_bf16"))
+        return rc;
     p.cB = a->B; p.cT = a->T; p.cH = a->H; p.cW = a->W; p.cCin = a->Cin;
     p.oT = pl.oT; p.oH = pl.oH; p.oW = pl.oW; p.sT = pl.sT; p.sHW = pl.sHW;
     p.tpad = pl.tpad;
@@ -1055,21 +1039,13 @@ extern "C" int ltxmi_gemm_kernel_id(const ltxmi_gemm_args* a) { return gemm_plan
 extern "C" int ltxmi_gemm_bf16(const ltxmi_gemm_args* a, void* stream) {
     const int kernel = gemm_plan(a, "ltxmi_gemm_bf16");
     if (kernel < 0) return kernel;
-    GemmParams p;
-    p.A = (const uint16_t*)a->A; p.lda = a->lda;
-    p.W = (const uint16_t*)a->W; p.ldw = a->ldw;
-    p.bias = a->bias ? (const uint16_t*)a->bias : zero_page_ptr();
-    p.bias_stride = a->bias ? 1 : 0;
-    LTXMI_REQUIRE(p.bias, LTXMI_ERR_LAUNCH, "ltxmi_gemm_bf16: cannot resolve the zero page");
-    p.C = (uint16_t*)a->C; p.ldc = a->ldc;
-    p.M = a->M; p.N = a->N; p.K = a->K;
+    GemmParams p = {};
+    if (const int rc = gemm_params(&p, a->A, a->lda, a->W, a->ldw, a->bias, a->C, a->ldc, a->M, a->N, a->K, "ltxmi_gemm_bf16")) return rc;
     p.R = (const uint16_t*)a->residual; p.ldr = a->ldr;
     p.gate_table = (const uint16_t*)a->gate_table;
     p.gate_temb = (const uint16_t*)a->gate_temb;
     p.gate_ld = a->gate_ld;
-    p.rows_per_group = a->rows_per_group > 0 ? a->rows_per_group : 1;
-    p.tiles_m = p.tiles_n = 0;
-    p.cB = p.cT = p.cH = p.cW = p.cCin = 1; p.oT = p.oH = p.oW = 1; p.sT = p.sHW = 1; p.tpad = 0; p.tzero = 0; p.pad_replicate = 0; p.res = nullptr; p.res_ch = 0;
+    if (a->rows_per_group > 0) p.rows_per_group = a->rows_per_group;
     // without a rowsumsq pointer the cols / ld fields are NOT read: the plain epilogue runs on the row-sums instance and
     // must see cols = 0 (its extra stores are then dropped) whatever a caller left in those fields
     p.sumsq = a->rowsumsq;

@@ -11,13 +11,13 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ltx-video-gpupoor_amd", "csrc")
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffast-math", "-fno-finite-math-only", "-mllvm",
-         "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-fhonor-infinities", "-Rpass-analysis=kernel-resource-usage",
-         "--cuda-device-only", "-c"]
+ATTN_EXTRA = ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-fhonor-infinities"]       # the Makefile's EXTRA of the attention files
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffast-math", "-fno-finite-math-only",
+         "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c"]
 
 
-def _usage(source, tmp_path):
-    out = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, os.path.join(CSRC, source), "-o", str(tmp_path / "o.o")],
+def _usage(source, tmp_path, extra=ATTN_EXTRA):
+    out = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, os.path.join(CSRC, source), "-o", str(tmp_path / "o.o")],
                          capture_output=True, text=True, cwd=CSRC, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     usage, name = {}, None
@@ -69,3 +69,50 @@ def test_generic_attention_kernel_does_not_spill(tmp_path):
         assert len(inst) == 1, name
         assert u["VGPRs Spill"] == 0 and u["ScratchSize [bytes/lane]"] == 0, (name, u)
         assert u["Occupancy [waves/SIMD]"] >= floor[inst[0]], (name, u)
+
+
+def _pinned(usage, pins, what):
+    """pins: {mangled template arguments: (VGPRs spilled, SGPRs spilled, scratch bytes per lane, waves per SIMD)}"""
+    kernels = {k: v for k, v in usage.items() if what in k}
+    assert len(kernels) == len(pins), sorted(kernels)
+    for inst, want in pins.items():
+        name = [k for k in kernels if what + "I" + inst + "E" in k]
+        assert len(name) == 1, (inst, sorted(kernels))
+        u = kernels[name[0]]
+        got = (u["VGPRs Spill"], u["SGPRs Spill"], u["ScratchSize [bytes/lane]"], u["Occupancy [waves/SIMD]"])
+        assert got == want, (name[0], got, want)
+
+
+def test_gemm_kernels_keep_their_spills_and_occupancy(tmp_path):
+    """Every instance of gemm.hip where the commit that introduced csrc/epilogue.h found it (tools/codegen_diff.py against its
+    parent: identical).  The persistent kernel lives with 68 .. 87 spilled VGPRs by design of its epilogue; a shared helper or an
+    edit beside it that moves these figures has changed the K loop's register allocation."""
+    usage = _usage("gemm.hip", tmp_path, extra=[])
+    # <BM, BN, WAVES_M, WAVES_N, EPI, MODE>: EPI 0 plain, 1 GELU, 2 SiLU, 3 gate + residual, 4 depth-to-space, 5 residual, 6 row sums;
+    # MODE 1 = the implicit-GEMM convolution
+    tile = {"Li128ELi128ELi2ELi2ELi0ELi0E": (0, 0, 0, 3), "Li128ELi128ELi2ELi2ELi0ELi1E": (0, 0, 0, 2),
+            "Li128ELi128ELi2ELi2ELi1ELi0E": (0, 0, 0, 3), "Li128ELi128ELi2ELi2ELi2ELi0E": (0, 0, 0, 3),
+            "Li128ELi128ELi2ELi2ELi3ELi0E": (0, 0, 0, 2), "Li128ELi128ELi2ELi2ELi4ELi1E": (0, 0, 0, 2),
+            "Li128ELi128ELi2ELi2ELi5ELi0E": (0, 0, 0, 2), "Li128ELi128ELi2ELi2ELi5ELi1E": (0, 0, 0, 2),
+            "Li128ELi128ELi2ELi2ELi6ELi0E": (0, 0, 0, 3),
+            "Li256ELi256ELi2ELi4ELi0ELi0E": (0, 0, 0, 2), "Li256ELi256ELi2ELi4ELi0ELi1E": (6, 0, 28, 2),
+            "Li256ELi256ELi2ELi4ELi1ELi0E": (0, 0, 0, 2), "Li256ELi256ELi2ELi4ELi2ELi0E": (0, 0, 0, 2),
+            "Li256ELi256ELi2ELi4ELi3ELi0E": (0, 0, 0, 2), "Li256ELi256ELi2ELi4ELi4ELi1E": (6, 0, 28, 2),
+            "Li256ELi256ELi2ELi4ELi5ELi0E": (0, 0, 0, 2), "Li256ELi256ELi2ELi4ELi5ELi1E": (6, 0, 28, 2),
+            "Li256ELi256ELi2ELi4ELi6ELi0E": (0, 0, 0, 2)}
+    _pinned(usage, tile, "gemm_bf16_nt_kernel")
+    # <BM, BN, WAVES_M, WAVES_N, EPI>
+    persistent = {"Li256ELi256ELi2ELi4ELi1E": (68, 15, 248, 2), "Li256ELi256ELi2ELi4ELi2E": (68, 13, 248, 2),
+                  "Li256ELi256ELi2ELi4ELi3E": (87, 29, 276, 2), "Li256ELi256ELi2ELi4ELi5E": (84, 17, 256, 2),
+                  "Li256ELi256ELi2ELi4ELi6E": (77, 21, 248, 2)}
+    _pinned(usage, persistent, "gemm_bf16_nt_persistent_kernel")
+
+
+def test_direct_convolution_kernels_do_not_spill(tmp_path):
+    """Every instance of conv_direct.hip as the same commit found it: no spill, no scratch; two workgroups of the four-wave form
+    (and two waves per SIMD of the eight-wave form) stay resident."""
+    usage = _usage("conv_direct.hip", tmp_path, extra=[])
+    _pinned(usage, {"Li%dE" % e: (0, 0, 0, 2) for e in range(3)}, "conv3d_direct_kernel")                 # <EPI>, eight waves
+    _pinned(usage, {"Li%dE" % e: (0, 0, 0, 2) for e in range(7)}, "conv3d_direct_v3_kernel")              # <EPI>, four waves
+    _pinned(usage, {"Li4ELi128E": (0, 0, 0, 8), "Li4ELi256E": (0, 0, 0, 8), "Li8ELi256E": (0, 0, 0, 8), "Li12ELi256E": (0, 0, 0, 8),
+                    "Li16ELi256E": (0, 0, 0, 8)}, "conv_split_finalize_kernel")                             # <CPT, NT>
