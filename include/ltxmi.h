@@ -22,7 +22,8 @@
  *     (0.2: rowsumsq*, a_kblock* of ltxmi_gemm_args; q_rowsumsq*, q_norm*, rope_*, o_segment*
  *     of ltxmi_attn_args; 0.3: q_rstd*; 0.4: conv3d post_*; 0.5: redo_counter, force_exact of ltxmi_attn_args, y_norm, workspace of ltxmi_conv3d_args;
  *     0.6: lse* of ltxmi_attn_args; 0.7: no field -- ltxmi_gemm_kernel_id, ltxmi_conv3d_route, ltxmi_gemm_args.algo = 256 is honoured for every
- *     shape, and the GEMM entry check refuses a bad epilogue and a residual / gate pointer off an 8-byte boundary),
+ *     shape, and the GEMM entry check refuses a bad epilogue and a residual / gate pointer off an 8-byte boundary;
+ *     0.8: no field -- ltxmi_norm_modulate_f32in_bf16 and ltxmi_gate_residual_f32, the row passes of the fp32 residual stream),
  *     and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
  *     switches its companion size / stride fields off whatever they hold.
@@ -135,6 +136,48 @@ int ltxmi_norm_modulate_bf16(const void* x, int64_t ldx, void* y, int64_t ldy,
                              const void* scale_table, const void* scale_temb,
                              const void* shift_table, const void* shift_temb,
                              int64_t temb_ld, int32_t rows_per_group, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * 0.8 -- the fp32 residual stream (`mixed_precision`: pipeline_ltx_video.py:1061,1152-1177, transformer3d.py:439-442).
+ * With mixed=True the reference keeps hidden_states, timestep and embedded_timestep in fp32 while every linear runs in
+ * bf16 under autocast.  Two row passes carry that stream between the bf16 GEMM / attention kernels; where each value is
+ * rounded follows the reference line by line.
+ *
+ * ltxmi_norm_modulate_f32in_bf16: ltxmi_norm_modulate_bf16 with x as fp32 rows (ldx in fp32 elements).  The norm of an
+ * fp32 tensor is fp32 (attention.py:233, 314; transformer3d.py:489), `scale_shift_table[None, None] + timestep` is
+ * bf16 + fp32 = fp32 (attention.py:239-246; transformer3d.py:491-499), `*= 1 + scale; += shift` is fp32
+ * (attention.py:248-249, 318-319; transformer3d.py:501): the row statistics, 1 + (scale_table[c] + scale_temb[g, c]) and
+ * shift_table[c] + shift_temb[g, c] are formed in fp32 from the unrounded stream and the bf16 operands, and the only
+ * rounding is the bf16 store -- autocast's cast at the linear that consumes the row.  Both norm kinds, LayerNorm's
+ * variance about the mean as above.  D % 8 == 0, D <= 8192; x, y and the tables 16-byte aligned, ldx % 4 == 0, ldy % 8
+ * == 0, temb_ld % 8 == 0 (else LTXMI_ERR_UNSUPPORTED and nothing is written).  y cannot alias x.
+ *
+ * ltxmi_gate_residual_f32: in place on the fp32 stream,  h[r, c] += gate(r, c) * y[r, c],  y bf16 (the output of to_out /
+ * ff.net[2]),  gate(r, c) = gate_table[c] + gate_temb[(r / rows_per_group) * gate_ld + c]  formed in fp32 (bf16 operands).
+ *   round_product = 1: gate * y is rounded to bf16 (nearest even) before the add -- `attn_output *= gate_msa` is in place
+ *                      on the bf16 attention output (attention.py:285), `hidden_states += attn_output` adds in fp32 (:288);
+ *   round_product = 0: the fp32 product is added -- the FF output was stored into the fp32 norm buffer (attention.py:340), so
+ *                      `ff_output *= gate_mlp` (:348) and the sum (:351) are fp32;
+ *   gate_table == NULL: h += y, cross-attention's `hidden_states += attn_output` (attention.py:310); gate_temb, gate_ld,
+ *                      rows_per_group and round_product are then ignored.
+ * h_bf16 (optional, NULL = off; row stride ld_h_bf16): receives bf16(h) of the updated row in the same pass -- the A operand
+ * of attn2's to_q, which autocast would cast from the stream (attention.py:294-309), without reading the stream back.
+ * Every step is one correctly rounded fp32 operation; with round_product = 0 the product and the sum are ONE fused
+ * multiply-add (the product is not rounded at all).  D % 8 == 0, D <= 8192, rows * D / 8 < 2^31; h, y, the gate operands and h_bf16 16-byte aligned,
+ * ldh % 4 == 0, ldy, gate_ld, ld_h_bf16 % 8 == 0 (else LTXMI_ERR_UNSUPPORTED).  LTXMI_ERR_INVALID_ARG: NULL h or y, a
+ * non-positive size, a gate_table without gate_temb or with rows_per_group <= 0, round_product outside {0, 1}, h / y /
+ * h_bf16 not three different buffers.  gate_temb must hold a row for every group: the index is not clamped.
+ * ------------------------------------------------------------------------------- */
+int ltxmi_norm_modulate_f32in_bf16(const float* x, int64_t ldx, void* y, int64_t ldy,
+                                   int32_t rows, int32_t D, float eps, int32_t kind,
+                                   const void* scale_table, const void* scale_temb,
+                                   const void* shift_table, const void* shift_temb,
+                                   int64_t temb_ld, int32_t rows_per_group, void* stream);
+
+int ltxmi_gate_residual_f32(float* h, int64_t ldh, const void* y, int64_t ldy, int32_t rows, int32_t D,
+                            const void* gate_table, const void* gate_temb, int64_t gate_ld,
+                            int32_t rows_per_group, int32_t round_product,
+                            void* h_bf16, int64_t ld_h_bf16, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * q/k RMSNorm across heads (+weight, eps) followed by interleaved-pair RoPE on the flat

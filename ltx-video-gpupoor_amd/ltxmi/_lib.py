@@ -83,6 +83,10 @@ SIGNATURES = {
     "ltxmi_gemm_kernel_id": (c_int, [ctypes.POINTER(GemmArgs)]),
     "ltxmi_norm_modulate_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "ltxmi_norm_modulate_f32in_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_int,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "ltxmi_gate_residual_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                        c_int, c_int, c_void_p, c_int64, c_void_p]),
     "ltxmi_rmsnorm_rope_bf16": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,
                                         c_int64, c_int, c_void_p]),
     "ltxmi_rmsnorm_rope_rstd_bf16": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p,

@@ -15,6 +15,10 @@ What differs is where the arithmetic runs:
   * to_out + ``*= gate`` + ``hidden += ..``     -> GEMM with the GATE_RESIDUAL epilogue (in place)
   * ff.net[0] (+GELU-tanh), ff.net[2] + gate + residual -> two GEMMs with fused epilogues
 The token-chunking of the feed-forward (:333-343) existed only to save VRAM and is dropped.
+
+An fp32 ``hidden_states`` selects the mixed-precision form of the block (the reference's ``mixed=True``): the same GEMM and
+attention kernels with plain epilogues, and the fp32 stream carried by ltxmi_norm_modulate_f32in_bf16 and
+ltxmi_gate_residual_f32 (``BasicTransformerBlock._forward_stream32``).  The bf16 form is untouched by it.
 """
 from enum import Enum, auto
 from typing import Optional
@@ -207,6 +211,10 @@ def _host_mask(mask):
 
 class AttnProcessor2_0:
     """attention.py:978-1173 on libltxmi kernels.
+
+    A processor that cannot serve the mixed-precision block -- it is called WITHOUT ``fused_residual`` there and must return the
+    plain bf16 ``to_out`` result -- defines ``refuse_fp32_stream()`` and raises in it: ``BasicTransformerBlock._forward_stream32``
+    calls that hook on ``attn1``'s processor before anything else (the sequence-parallel processors of ltxmi.distributed do).
 
     ``fused_residual = (residual, gate_table, gate_temb, rows_per_group)`` (an extension used
     by BasicTransformerBlock) folds ``to_out`` + gate + ``residual += ..`` into one GEMM
@@ -427,6 +435,10 @@ class BasicTransformerBlock(nn.Module):
         def chunk(i):                                     # (table row, temb column block) of ada value i
             return table[i], temb[:, i * D:(i + 1) * D]
 
+        if hidden_states.dtype == torch.float32:
+            return self._forward_stream32(hidden_states, chunk, rpg, freqs_cis, encoder_hidden_states,
+                                          encoder_attention_mask, skip_layer_mask, host_mask, skip_layer_strategy)
+
         # 0/1. norm1 -> modulate(shift_msa=0, scale_msa=1) -> self-attention -> gate_msa(2) + residual
         norm_h = torch.empty_like(hidden_states)
         sc_t, sc_e = chunk(1)
@@ -463,4 +475,56 @@ class BasicTransformerBlock(nn.Module):
 
         if block_skip:
             ops.stg_blend_(hidden_states, original, skip_layer_mask.reshape(B).to(torch.float32))
+        return hidden_states
+
+    def _forward_stream32(self, hidden_states, chunk, rpg, freqs_cis, encoder_hidden_states, encoder_attention_mask,
+                          skip_layer_mask, host_mask, skip_layer_strategy):
+        """The block on an fp32 residual stream (the reference's ``mixed=True``: transformer3d.py:439-442 upcasts the stream,
+        autocast keeps every linear in bf16).  The GEMMs and attention are the bf16 path's, with plain epilogues; the stream
+        is touched by two row kernels only, which round where the reference rounds (include/ltxmi.h, 0.8):
+          norm1 / norm2      fp32 statistics and modulation, one rounding at the linear's input   (attention.py:233-251, 314-320)
+          attn1 residual     bf16(gate_msa * attn_output), added in fp32                          (:285, :288)
+          attn2              reads bf16(stream) -- written by attn1's residual pass --, added in fp32  (:294-310)
+          FF residual        fp32 gate_mlp * ff_output, added in fp32                             (:340, :348, :351)"""
+        refuse = getattr(self.attn1.processor, "refuse_fp32_stream", None)
+        if refuse is not None:                                      # the sequence-parallel processors (ltxmi.distributed)
+            refuse()
+        B, N, D = hidden_states.shape
+        h2 = hidden_states.view(B * N, D)
+        norm_h = torch.empty((B, N, D), dtype=BF16, device=hidden_states.device)
+        sc_t, sc_e = chunk(1)
+        sh_t, sh_e = chunk(0)
+        ops.norm_modulate_f32in(h2, norm_h.view(B * N, D), self.norm1.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
+        attn_out = self.attn1([norm_h], freqs_cis=freqs_cis, skip_layer_mask=skip_layer_mask,
+                              skip_layer_strategy=skip_layer_strategy)
+        g_t, g_e = chunk(2)
+        h_bf16 = norm_h if self.attn2 is not None else None         # norm1's output is consumed: its buffer takes bf16(stream)
+        ops.gate_residual_f32_(h2, attn_out.view(B * N, D), g_t, g_e, rpg, round_product=1,
+                               h_bf16=None if h_bf16 is None else h_bf16.view(B * N, D))
+        del attn_out, norm_h
+
+        if self.attn2 is not None:
+            attn_out = self.attn2([h_bf16], freqs_cis=freqs_cis, encoder_hidden_states=encoder_hidden_states,
+                                  attention_mask=encoder_attention_mask)
+            ops.gate_residual_f32_(h2, attn_out.view(B * N, D))
+            del attn_out, h_bf16
+
+        block_skip = (host_mask is not None and skip_layer_strategy == SkipLayerStrategy.TransformerBlock)
+        if block_skip:
+            original = hidden_states.clone()                        # as in forward: the state the reference's alias holds
+
+        norm_h = torch.empty((B * N, D), dtype=BF16, device=hidden_states.device)
+        sc_t, sc_e = chunk(4)
+        sh_t, sh_e = chunk(3)
+        ops.norm_modulate_f32in(h2, norm_h, self.norm2.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
+        ff1 = ops.gemm(norm_h, self.ff.net[0].proj.weight, self.ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH)
+        ff2 = ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=norm_h)
+        del ff1
+        g_t, g_e = chunk(5)
+        ops.gate_residual_f32_(h2, ff2, g_t, g_e, rpg, round_product=0)
+        del ff2, norm_h
+
+        if block_skip:
+            m = skip_layer_mask.reshape(B, 1, 1).to(torch.float32)  # fp32 rows blended in torch (attention.py:355-362)
+            hidden_states.mul_(m).add_(original * (1.0 - m))
         return hidden_states

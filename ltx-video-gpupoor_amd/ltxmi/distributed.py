@@ -187,6 +187,13 @@ def ring_attn_forward(qkv, softmax_scale, group=None, attn_fn: Optional[Callable
 
 
 # ------------------------------------------------------------------ processor + model forward
+def _refuse_fp32_stream(who):
+    """Sequence parallelism is built for the bf16 residual stream only: the shards' gate + residual ride in the to_out GEMM's
+    epilogue, and nothing here carries an fp32 stream between the exchanges."""
+    raise NotImplementedError(f"ltxmi.distributed.{who}: mixed=True (the fp32 residual stream of mixed_precision) is not "
+                              "built for sequence parallelism; run it on one GPU or use the bf16 stream")
+
+
 class UlyssesAttnProcessor:
     """Replaces AttnProcessor2_0 on ``attn1`` of every block (installed with ``Attention.set_processor``): identical
     math, plus the two all-to-alls -- which run directly on the buffers the kernels write and read:
@@ -206,7 +213,10 @@ class UlyssesAttnProcessor:
     the AttentionValues strategy (skip attention and return v, attention.py:1060-1062) is not taken -- attention always
     runs and the STG blend then selects v for the perturbed rows: the same values, and every rank issues the same
     collectives whatever its rows are; (2) an ``attention_mask`` for self-attention is not supported (the reference's
-    LTX path never passes one, transformer3d.py:411-415 builds the mask for the text keys only)."""
+    LTX path never passes one, transformer3d.py:411-415 builds the mask for the text keys only).
+
+    ``refuse_fp32_stream``: the hook ``BasicTransformerBlock._forward_stream32`` calls on ``attn1``'s processor, if it has one,
+    before it touches an fp32 residual stream (``mixed=True``); this processor raises there."""
 
     def __init__(self, group=None, exchange_at_world_1=None, simulate_world=None):
         """``simulate_world`` (bench.py's compute-only projection, never a product setting): run ONE rank's share of a
@@ -223,6 +233,9 @@ class UlyssesAttnProcessor:
             exchange_at_world_1 = os.environ.get("LTXMI_SP_FORCE_EXCHANGE", "0") == "1"
         self.exchange_at_world_1 = bool(exchange_at_world_1)
         self.simulate_world = int(simulate_world) if simulate_world else None
+
+    def refuse_fp32_stream(self):
+        _refuse_fp32_stream("UlyssesAttnProcessor")
 
     def __call__(self, attn, hidden_states_wrapper, freqs_cis, encoder_hidden_states=None,
                  attention_mask=None, temb=None, skip_layer_mask=None, skip_layer_strategy=None,
@@ -292,10 +305,13 @@ class RingAttnProcessor(AttnProcessor2_0):
     finalises q's row factor), q's norm + RoPE applied by the attention kernel on load; every head is on every rank, so
     the across-heads RMSNorm needs no exchange -- and the attention call becomes ``ring_attention`` over the group.  STG
     blends, ``to_out`` and its fused gate / residual epilogue follow unchanged.  Cross-attention (text keys replicated on
-    every rank, queries sharded) stays the local call."""
+    every rank, queries sharded) stays the local call.  ``refuse_fp32_stream``: as on ``UlyssesAttnProcessor``."""
 
     def __init__(self, group=None):
         self.group = group
+
+    def refuse_fp32_stream(self):
+        _refuse_fp32_stream("RingAttnProcessor")
 
     def attend(self, qkv_list, is_cross, **kw):
         if is_cross:
@@ -444,6 +460,8 @@ def usp_dit_forward(model, hidden_states, freqs_cis, encoder_hidden_states=None,
     The NAME is the reference's (wan/distributed/xdit_context_parallel.py:66), the signature is not: there it is a
     replacement for ``WanModel.forward(self, x, t, context, seq_len, clip_fea=None, y=None)`` -- a model outside this
     path -- and here it wraps ``Transformer3DModel.forward`` and so takes THAT method's arguments."""
+    if kw.get("mixed"):
+        _refuse_fp32_stream("usp_dit_forward")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     N = hidden_states.shape[1]
     hs = shard_tokens(hidden_states, rank, world)

@@ -199,6 +199,57 @@ def norm_modulate(x, out, eps, kind, scale_table, scale_temb, shift_table, shift
     return out
 
 
+def _chk_f32(t, what):
+    if t.dtype != torch.float32 or not t.is_cuda:
+        raise TypeError(f"ltxmi.{what}: expected a CUDA float32 tensor, got {t.dtype} on {t.device}")
+
+
+def norm_modulate_f32in(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):
+    """``norm_modulate`` for the fp32 residual stream (mixed precision): x fp32 rows, out bf16 rows, the statistics and the
+    modulation in fp32 from the unrounded stream, one rounding at the store (include/ltxmi.h)."""
+    _chk_f32(x, "norm_modulate_f32in")
+    _chk_bf16(out, scale_table, scale_temb, shift_table, shift_temb)
+    x2, rows, ldx = _rows(x)
+    o2, orows, ldy = _rows(out)
+    D = x2.shape[1]
+    if orows != rows or o2.shape[1] != D:
+        raise ValueError("ltxmi.norm_modulate_f32in: out must have x's rows and channels")
+    if scale_temb.stride(0) != shift_temb.stride(0):
+        raise ValueError("ltxmi.norm_modulate_f32in: scale/shift tables must share a row stride")
+    check(lib.ltxmi_norm_modulate_f32in_bf16(_ptr(x2), ldx, _ptr(o2), ldy, rows, D, eps, kind,
+                                             _ptr(scale_table), _ptr(scale_temb), _ptr(shift_table), _ptr(shift_temb),
+                                             scale_temb.stride(0), rows_per_group, _stream()),
+          "ltxmi_norm_modulate_f32in_bf16")
+    return out
+
+
+def gate_residual_f32_(h, y, gate_table=None, gate_temb=None, rows_per_group=1, round_product=0, h_bf16=None):
+    """In place on the fp32 stream: h += (gate_table + gate_temb[group]) * y, y bf16 rows; gate_table None: h += y.
+    gate_temb: 2-D view [groups, D].  round_product=1 rounds the product to bf16 before the add (the reference's in-place
+    ``attn_output *= gate_msa``), 0 keeps it fp32 (its FF gate).  h_bf16 (bf16 rows): also receives bf16(h) of the result."""
+    _chk_f32(h, "gate_residual_f32_")
+    _chk_bf16(y, gate_table, gate_temb, h_bf16)
+    h2, rows, ldh = _rows(h)
+    y2, yrows, ldy = _rows(y)
+    D = h2.shape[1]
+    if yrows != rows or y2.shape[1] != D:
+        raise ValueError("ltxmi.gate_residual_f32_: y must have h's rows and channels")
+    if (gate_table is None) != (gate_temb is None):
+        raise ValueError("ltxmi.gate_residual_f32_: gate_table and gate_temb go together")
+    gate_ld = 0
+    if gate_temb is not None:
+        gate_ld = gate_temb.stride(0) if gate_temb.dim() == 2 else 0
+    b2, ldb = None, 0
+    if h_bf16 is not None:
+        b2, brows, ldb = _rows(h_bf16)
+        if brows != rows or b2.shape[1] != D:
+            raise ValueError("ltxmi.gate_residual_f32_: h_bf16 must have h's rows and channels")
+    check(lib.ltxmi_gate_residual_f32(_ptr(h2), ldh, _ptr(y2), ldy, rows, D, _ptr(gate_table), _ptr(gate_temb), gate_ld,
+                                      rows_per_group, int(round_product), _ptr(b2), ldb, _stream()),
+          "ltxmi_gate_residual_f32")
+    return h
+
+
 def rmsnorm_rope_(x, weight, eps, cos=None, sin=None, rope_period=0, rstd_of=None):
     """In place: x = rope(rmsnorm(x) * weight).  x: 2-D row-strided view [rows, D];
     cos/sin: [period, D] tables (row r uses row r % period) or None.

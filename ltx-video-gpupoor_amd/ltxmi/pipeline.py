@@ -357,14 +357,13 @@ class LTXVideoPipeline:
         return gs, stg, rs, skip_block_list
 
     @staticmethod
-    def _refuse_outside_this_path(prompt, prompt_embeds, is_video, mixed_precision, offload_to_cpu, num_videos):
+    def _refuse_outside_this_path(prompt, prompt_embeds, is_video, offload_to_cpu, num_videos):
         """What the reference's ``__call__`` takes and this one does not."""
         _refuse([(refused, NotImplementedError, message) for refused, message in [
             (prompt is not None or prompt_embeds is None,
              "__call__ takes prompt_embeds / prompt_attention_mask (as the reference's loop does, :1029-1051); string "
              "prompts go through encode_prompt / LTXMultiScalePipeline with the caller's T5"),
             (not is_video, "is_video=False (single images, video_scale_factor 1) is outside this path"),
-            (mixed_precision, "mixed_precision=True (fp32 latents under autocast, :1153-1156) is not on this path"),
             (offload_to_cpu, "offload_to_cpu is not on this path (everything is resident in HBM)"),
             (num_videos != 1,
              "one prompt and one video per call on this path (the reference's CFG-star broadcast at "
@@ -476,7 +475,11 @@ class LTXVideoPipeline:
 
         Explicit refusals (outside this path): a string ``prompt`` (the reference's ``__call__`` does not encode it
         either: it reads ``prompt_embeds``, :1029-1051 -- ``LTXMultiScalePipeline`` / ``encode_prompt`` do), ``is_video=False``,
-        ``mixed_precision``, ``offload_to_cpu``, ``enhance_prompt``, more than one prompt / image per prompt.
+        ``offload_to_cpu``, ``enhance_prompt``, more than one prompt / image per prompt.
+
+        ``mixed_precision=True`` (:1061, :1152-1156, :1177): the latents are fp32 whatever ``prompt_embeds``' dtype is, and the
+        transformer runs with ``mixed=True`` -- an fp32 residual stream between bf16 linears and attention, a bf16
+        ``noise_pred``; guidance and the scheduler step update the fp32 latents.
 
         Keyword-only extensions behind the reference's parameters: ``stg_row_dedup`` (the STG "perturbed" row has the text
         row's inputs, so it is the text row until the step's first skipped block; those blocks run on one row less and the
@@ -489,8 +492,14 @@ class LTXVideoPipeline:
         image_cond_noise_scale = kwargs.get("image_cond_noise_scale", 0.0)
         self.check_inputs(prompt, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds,
                           prompt_attention_mask, negative_prompt_attention_mask, enhance_prompt)
-        self._refuse_outside_this_path(prompt, prompt_embeds, is_video, mixed_precision, offload_to_cpu,
+        self._refuse_outside_this_path(prompt, prompt_embeds, is_video, offload_to_cpu,
                                        num_images_per_prompt * (0 if prompt_embeds is None else prompt_embeds.shape[0]))
+        if mixed_precision:
+            # :1061: fp32 latents whatever the prompt's dtype; the transformer then keeps its residual stream in fp32 (:1177)
+            if latents_dtype not in (None, torch.float32):
+                raise ValueError(f"ltxmi.LTXVideoPipeline: mixed_precision=True keeps the latents in float32 "
+                                 f"(pipeline_ltx_video.py:1061); latents_dtype={latents_dtype} contradicts it")
+            latents_dtype = torch.float32
         tr, device = self.transformer, self._execution_device
         holder = self if ltxv_model is None else ltxv_model                              # of ``_interrupt``
 

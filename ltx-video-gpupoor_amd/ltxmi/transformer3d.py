@@ -283,11 +283,12 @@ class Transformer3DModel(nn.Module):
         B - 1 and B rows would be served by different self-attention kernels (``ops.attention_kernel_id``).
         ``_microbatches`` (extension, set by ltxmi.distributed): a list of batch-row slices; the block loop then runs
         every block once per slice, each slice on a stream of its own, so that one slice's collectives (sequence
-        parallelism) are hidden behind the other slices' kernels.  Rows are independent: same result."""
+        parallelism) are hidden behind the other slices' kernels.  Rows are independent: same result.
+        ``mixed`` (transformer3d.py:439-442): the residual stream is fp32 from the input projection to the output norm, the
+        linears, q/k norms and attention stay bf16 (``BasicTransformerBlock._forward_stream32``); the output is bf16 either
+        way.  Sequence parallelism (ltxmi.distributed) refuses it."""
         if self.dtype != BF16:
             raise TypeError("ltxmi.Transformer3DModel runs in bfloat16 only: call .to(torch.bfloat16)")
-        if mixed:
-            raise NotImplementedError("mixed (fp32 residual stream) precision is not on this path")
         if attention_mask is not None:
             raise NotImplementedError("a self-attention mask is not on this path")
         dtype = self.dtype
@@ -312,6 +313,11 @@ class Transformer3DModel(nn.Module):
         temb, embedded_timestep = self.adaln_single(timestep.flatten())
         temb = temb.view(B, -1, 6 * D)
         embedded_timestep = embedded_timestep.view(B, -1, D)
+        if mixed:
+            # transformer3d.py:439-442: the residual stream goes to fp32 here (exact: the values are bf16's) and stays fp32
+            # through the blocks and the output norm.  `timestep` and `embedded_timestep` are upcast there too: their values
+            # stay bf16's, and the row kernels of the fp32 stream widen them on load, so they keep their storage.
+            hidden_states = hidden_states.float()
 
         # 2. text projection
         if self.caption_projection is not None:
@@ -404,9 +410,14 @@ class Transformer3DModel(nn.Module):
         # 3. output: LayerNorm (no affine, 1e-6) -> (1 + scale) x + shift -> proj_out (:489-503)
         T1 = embedded_timestep.shape[1]
         emb2 = embedded_timestep.reshape(B * T1, D)
-        normed = torch.empty_like(hidden_states)
-        ops.norm_modulate(hidden_states.view(B * N, D), normed.view(B * N, D), 1e-6, ops.NORM_LAYER,
-                          self.scale_shift_table[1], emb2, self.scale_shift_table[0], emb2, N // T1)
+        if mixed:
+            normed = torch.empty((B, N, D), dtype=dtype, device=hidden_states.device)
+            ops.norm_modulate_f32in(hidden_states.view(B * N, D), normed.view(B * N, D), 1e-6, ops.NORM_LAYER,
+                                    self.scale_shift_table[1], emb2, self.scale_shift_table[0], emb2, N // T1)
+        else:
+            normed = torch.empty_like(hidden_states)
+            ops.norm_modulate(hidden_states.view(B * N, D), normed.view(B * N, D), 1e-6, ops.NORM_LAYER,
+                              self.scale_shift_table[1], emb2, self.scale_shift_table[0], emb2, N // T1)
         out = ops.gemm(normed.view(B * N, D), self.proj_out.weight, self.proj_out.bias).view(B, N, -1)
         if not return_dict:
             return (out,)
