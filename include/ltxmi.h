@@ -338,7 +338,12 @@ int ltxmi_stg_blend_grouped_bf16(void* a, const void* v, int64_t v_stride_g, int
  * folded into the address computation:
  *   time:  replicate (k-1) frames in front when causal, else (k-1)/2 on both sides
  *          ltx_video/models/autoencoders/causal_conv3d.py:44-59
- *   space: pad 1, zeros or replicate (nn.Conv3d padding_mode)   causal_conv3d.py:33-42
+ *   space: pad 1, zeros, replicate or reflect (nn.Conv3d padding_mode)   causal_conv3d.py:33-42
+ *          reflect is torch's: index -1 reads index 1 and index L reads index L - 2 (the edge is not
+ *          repeated), H and W each on their own, so a corner mirrors on both; it needs H >= 2 and W >= 2.
+ *          The time axis is never mirrored: replicated frames, or zeros with time_pad_zeros.
+ *          The mode chooses nothing else: route, channel split, post_norm fusion and workspace are those
+ *          of the same call with any other mode.
  * With strides the output grid is nn.Conv3d's: floor((L + pad - 3) / stride) + 1 per axis.
  * x: [B, T, H, W, Cin]; w: [Cout, 27, Cin] (tap-major, K contiguous; repacked from the
  * checkpoint's [Cout,Cin,3,3,3] once at load); bias [Cout]; y: [B, T, H, W, Cout].
@@ -352,7 +357,9 @@ typedef struct ltxmi_conv3d_args {
     const void* x; const void* w; const void* bias; void* y;
     int32_t B, T, H, W, Cin, Cout;
     int32_t causal;            /* 1: replicate 2 frames in front; 0: 1 + 1                */
-    int32_t pad_replicate;     /* spatial padding mode: 0 zeros, 1 replicate              */
+    int32_t pad_replicate;     /* spatial padding MODE (the name is older than the third value): 0 zeros, 1 replicate,
+                                  2 reflect (0.9); anything else, or reflect with H < 2 or W < 2, is
+                                  LTXMI_ERR_INVALID_ARG                                    */
     int32_t d2s;               /* 0 plain NDHWC store, 1 depth-to-space (2,2,2) store     */
     const void* residual;      /* d2s only: x itself (pre-conv block input) or NULL       */
     int32_t res_channels;      /* channels of the residual tensor (Cin of the block)      */

@@ -24,6 +24,29 @@ int conv3d_gemm_tile(int64_t M, int Cout);     // gemm.hip: the implicit GEMM's 
 int launch_conv3d_gemm(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream);       // gemm.hip
 int launch_conv3d_direct(const ltxmi_conv3d_args* a, const ConvPlan& pl, hipStream_t stream);     // conv_direct.hip
 
+// ltxmi_conv3d_args.pad_replicate: the spatial padding mode (nn.Conv3d padding_mode with padding 1)
+enum ConvPad : int { CONV_PAD_ZEROS = 0, CONV_PAD_REPLICATE = 1, CONV_PAD_REFLECT = 2 };
+
+// Where coordinate i of an axis of extent L (H or W; each on its own, so a corner mirrors on both) is read from: the source
+// index, always in [0, L - 1], and whether the element is zero padding instead.  Only i = -1 and i = L are padding (reflect:
+// -1 reads 1 and L reads L - 2, the edge is not repeated; the entry check refuses L < 2); tiles and M-rows overhang the image
+// further, into positions whose outputs are never stored, and there a mirror 2 L - 2 - i would leave the buffer (L = 2, i = 9:
+// -7): every i beyond L reads what i = L reads, whatever the mode.
+// The mirror is the clamp moved one step back inside: + 1 in the lanes below 0, - 1 in the lanes from L on.  Written as an add
+// with carry and a subtract with borrow whose carry-in is the lane mask of the compare, it works on the clamped value in place.
+// The implicit GEMM's gather (gemm.hip, in the K loop of a kernel that lives at 256 registers) has none to spare: as selects or
+// as arithmetic on i (2 clamp(i) - i) every C++ form of it cost the 256-wide instances one to seven more spilled registers.
+struct ConvSrc { int i; bool zero; };
+__device__ __forceinline__ ConvSrc conv_pad_src(int i, int L, int mode) {
+    const bool lo = i < 0, hi = i >= L, mirror = mode == CONV_PAD_REFLECT && L > 1;
+    int s = lo ? 0 : (hi ? L - 1 : i);
+    const uint64_t up = __builtin_amdgcn_ballot_w64(lo && mirror), down = __builtin_amdgcn_ballot_w64(hi && mirror);
+    uint64_t carry_out;                                              // (never read)
+    asm("v_addc_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(s), "=s"(carry_out) : "s"(up));
+    asm("v_subb_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(s), "=s"(carry_out) : "s"(down));
+    return ConvSrc{s, (lo | hi) && mode == CONV_PAD_ZEROS};
+}
+
 // the direct forms' output tile: 2 (t) x 8 x 16 positions x 128 output channels
 constexpr int CONV_TT = 2, CONV_TY = 8, CONV_TX = 16;
 

@@ -69,12 +69,10 @@ __global__ __launch_bounds__(512) void conv3d_direct_kernel(ConvDirectP p) {
             const int hx = r % G::HX, hy = (r / G::HX) % G::HY, ht = r / (G::HX * G::HY);
             int ti = t0 + ht - p.tpad, yi = y0 + hy - 1, xi = x0 + hx - 1;
             const bool toob = (ti < 0) | (ti >= p.T);
-            const bool oob = (yi < 0) | (yi >= p.H) | (xi < 0) | (xi >= p.W);
             ti = ti < 0 ? 0 : (ti >= p.T ? p.T - 1 : ti);
-            yi = yi < 0 ? 0 : (yi >= p.H ? p.H - 1 : yi);
-            xi = xi < 0 ? 0 : (xi >= p.W ? p.W - 1 : xi);
-            const int64_t e = xb + ((int64_t)(ti * p.H + yi) * p.W + xi) * p.Cin;
-            const bool zero = (oob && !p.pad_replicate) | (toob && p.tzero);
+            const ConvSrc sy = conv_pad_src(yi, p.H, p.pad_replicate), sx = conv_pad_src(xi, p.W, p.pad_replicate);
+            const int64_t e = xb + ((int64_t)(ti * p.H + sy.i) * p.W + sx.i) * p.Cin;
+            const bool zero = sy.zero | sx.zero | (toob && p.tzero);
             rowtab[r] = zero ? 0x7ffffff0u : (uint32_t)(e * 2);
         }
     }
@@ -455,12 +453,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_direct_v3_kernel(ConvDirectP p)
             const int hy = rr / G::HX, hx = rr - hy * G::HX;
             int ti = t0 + ht - p.tpad, yi = img_y(hy - 1, hx - 1), xi = img_x(hy - 1, hx - 1);
             const bool toob = (ti < 0) | (ti >= p.T);
-            const bool oob = (yi < 0) | (yi >= p.H) | (xi < 0) | (xi >= p.W);
             ti = ti < 0 ? 0 : (ti >= p.T ? p.T - 1 : ti);
-            yi = yi < 0 ? 0 : (yi >= p.H ? p.H - 1 : yi);
-            xi = xi < 0 ? 0 : (xi >= p.W ? p.W - 1 : xi);
-            const int64_t e = xb + ((int64_t)(ti * p.H + yi) * p.W + xi) * p.Cin;
-            const bool zero = (oob && !p.pad_replicate) | (toob && p.tzero) | (rr >= G::PLANE_ROWS);
+            const ConvSrc sy = conv_pad_src(yi, p.H, p.pad_replicate), sx = conv_pad_src(xi, p.W, p.pad_replicate);
+            const int64_t e = xb + ((int64_t)(ti * p.H + sy.i) * p.W + sx.i) * p.Cin;
+            const bool zero = sy.zero | sx.zero | (toob && p.tzero) | (rr >= G::PLANE_ROWS);
             rowtab[r] = zero ? 0x7ffffff0u : (uint32_t)(e * 2);
         }
     }

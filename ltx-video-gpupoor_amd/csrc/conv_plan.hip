@@ -122,6 +122,13 @@ static int conv3d_check(const ltxmi_conv3d_args* a, ConvPlan* plan) {
     LTXMI_REQUIRE(a && a->x && a->w && a->y, LTXMI_ERR_INVALID_ARG, "ltxmi_conv3d_ndhwc_bf16: NULL argument");
     LTXMI_REQUIRE(a->B > 0 && a->T > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_conv3d_ndhwc_bf16: non-positive shape");
+    // the spatial padding mode: it chooses nothing in the plan (a reflect call runs on the route of its replicate twin)
+    LTXMI_REQUIRE(a->pad_replicate >= CONV_PAD_ZEROS && a->pad_replicate <= CONV_PAD_REFLECT, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_conv3d_ndhwc_bf16: pad_replicate = %d is no spatial padding mode (0 zeros, 1 replicate, 2 reflect)",
+                  a->pad_replicate);
+    LTXMI_REQUIRE(a->pad_replicate != CONV_PAD_REFLECT || (a->H >= 2 && a->W >= 2), LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_conv3d_ndhwc_bf16: reflect padding needs H >= 2 and W >= 2 (got %d x %d): the mirror of a "
+                  "single row or column does not exist", a->H, a->W);
     const ConvPlan pl = *plan = conv3d_plan(a);
     LTXMI_REQUIRE(a->Cin % 64 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cin=%d must be a multiple of 64", a->Cin);
     LTXMI_REQUIRE(a->Cout % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_conv3d_ndhwc_bf16: Cout=%d must be a multiple of 8", a->Cout);

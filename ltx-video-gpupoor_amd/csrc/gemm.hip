@@ -164,12 +164,10 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(Gem
             int tt = cv_t[j] + dt - p.tpad;
             const bool toob = (tt < 0) | (tt >= p.cT);
             tt = tt < 0 ? 0 : (tt >= p.cT ? p.cT - 1 : tt);          // time: replicate (CausalConv3d)
-            int yy = cv_y[j] + dy - 1, xx = cv_x[j] + dx - 1;
-            const bool oob = (yy < 0) | (yy >= p.cH) | (xx < 0) | (xx >= p.cW);
-            yy = yy < 0 ? 0 : (yy >= p.cH ? p.cH - 1 : yy);
-            xx = xx < 0 ? 0 : (xx >= p.cW ? p.cW - 1 : xx);
-            const uint16_t* src = a_src[j] + ((int64_t)(tt * p.cH + yy) * p.cW + xx) * p.cCin + c0;
-            if ((oob && !p.pad_replicate) | (toob && p.tzero)) src = (const uint16_t*)g_zero_page;
+            const ConvSrc sy = conv_pad_src(cv_y[j] + dy - 1, p.cH, p.pad_replicate);      // space: zeros / replicate / reflect
+            const ConvSrc sx = conv_pad_src(cv_x[j] + dx - 1, p.cW, p.pad_replicate);
+            const uint16_t* src = a_src[j] + ((int64_t)(tt * p.cH + sy.i) * p.cW + sx.i) * p.cCin + c0;
+            if (sy.zero | sx.zero | (toob && p.tzero)) src = (const uint16_t*)g_zero_page;
             glds16(src, sa + (wave * A_INSTR + j) * 1024);
         }
     };

@@ -93,6 +93,9 @@ class CausalConv3d(nn.Module):
     (conv_in of the encoder has 48 input channels, its conv_out 129 outputs); the result then has
     ``cout_padded`` channels and the caller reads the first ``out_channels``."""
 
+    # nn.Conv3d's padding_mode, which the reference hands spatial_padding_mode to ("circular": no LTX config uses it)
+    _PAD_MODES = {"zeros": ops.PAD_ZEROS, "replicate": ops.PAD_REPLICATE, "reflect": ops.PAD_REFLECT}
+
     def __init__(self, in_channels, out_channels, kernel_size: int = 3, stride=1, dilation=1, groups=1,
                  spatial_padding_mode: str = "zeros", **kwargs):
         super().__init__()
@@ -100,12 +103,15 @@ class CausalConv3d(nn.Module):
         if kernel_size != 3 or dilation != 1 or groups != 1 or any(s not in (1, 2) for s in stride) \
                 or stride[1] != stride[2]:
             raise NotImplementedError("ltxmi.CausalConv3d: only dense 3x3x3 with strides 1/2 is on this path")
-        if spatial_padding_mode not in ("zeros", "replicate"):
-            raise NotImplementedError(f"spatial_padding_mode {spatial_padding_mode}")
+        if spatial_padding_mode not in self._PAD_MODES:
+            raise NotImplementedError(f"ltxmi.CausalConv3d: spatial_padding_mode {spatial_padding_mode!r} is not on this path "
+                                      f"(zeros, replicate and reflect are)")
         self.in_channels, self.out_channels = in_channels, out_channels
         self.cin_padded, self.cout_padded = -(-in_channels // 64) * 64, -(-out_channels // 8) * 8
         self.stride = stride
         self.time_kernel_size = 3
+        self.spatial_padding_mode = spatial_padding_mode
+        self.pad_mode = self._PAD_MODES[spatial_padding_mode]          # what the kernel is given
         self.pad_replicate = spatial_padding_mode == "replicate"
         self.conv = _Conv3dParams(in_channels, out_channels, 3)
         self._packed = None
@@ -156,7 +162,7 @@ class CausalConv3d(nn.Module):
         w, b = self.packed(d2s)
         if post_norm is not None and self.cout_padded != self.out_channels:
             raise ValueError("ltxmi.CausalConv3d: post_norm on a convolution with padded output channels")
-        return ops.conv3d(x, w, b, causal, self.pad_replicate, d2s=d2s, residual=residual, add=add,
+        return ops.conv3d(x, w, b, causal, self.pad_mode, d2s=d2s, residual=residual, add=add,
                           stride=self.stride, tpad=tpad, out_T=out_T, post_norm=post_norm, keep_raw=keep_raw)
 
 

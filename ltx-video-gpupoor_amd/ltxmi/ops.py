@@ -520,6 +520,10 @@ CONV_SPLIT = True
 _conv_workspace = {}
 
 
+# conv3d(pad_replicate=...): the spatial padding mode, ltxmi_conv3d_args.pad_replicate (False / True are the first two)
+PAD_ZEROS, PAD_REPLICATE, PAD_REFLECT = 0, 1, 2
+
+
 def _conv3d_args(x, w_packed, bias, causal, pad_replicate, d2s, residual, add, out, stride, tpad, out_T, kernel_t,
                  time_pad_zeros, algo, post_norm, keep_raw, workspace, out_norm, launch):
     """The ltxmi_conv3d_args of a ``conv3d`` / ``conv3d_route`` call -> (args, out, out_norm, second_launch, key).  ``launch``
@@ -621,7 +625,10 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
     activated one (the NEXT block's norm1 -> AdaLN -> SiLU riding on this convolution: ltxmi_conv3d_args.y_norm); allowed
     with `add` and with d2s.
     workspace: a uint8 device tensor to use as ltxmi_conv3d_args.workspace instead of the module's own buffer; out_norm: where
-    keep_raw's activated output goes (allocated if None)."""
+    keep_raw's activated output goes (allocated if None).
+    pad_replicate: the spatial padding mode -- PAD_ZEROS / PAD_REPLICATE / PAD_REFLECT (0 / 1 / 2; False / True mean the first
+    two).  Reflect is torch's (index -1 reads index 1, the edge is not repeated) and needs H, W >= 2; the time axis is never
+    mirrored."""
     a, out, out_norm, second_launch, keys = _conv3d_args(x, w_packed, bias, causal, pad_replicate, d2s, residual, add, out, stride,
                                                          tpad, out_T, kernel_t, time_pad_zeros, algo, post_norm, keep_raw,
                                                          workspace, out_norm, True)
