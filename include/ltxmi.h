@@ -315,14 +315,16 @@ int ltxmi_qkv_norm_rope_pack_bf16(const void* qkv, int64_t ld, int32_t B, int32_
 /* ---------------------------------------------------------------------------------
  * Small elementwise helpers on the DiT path.
  * ------------------------------------------------------------------------------- */
-/* y = silu(x) (kind 0) -- AdaLayerNormSingle's SiLU between its linears, transformer3d.py:428. */
+/* y = silu(x) (kind 0) -- AdaLayerNormSingle's SiLU between its linears, transformer3d.py:428.
+ * x, y dense; n % 8 == 0, x and y 16-byte aligned (else LTXMI_ERR_UNSUPPORTED and nothing is written).  y may be x. */
 int ltxmi_silu_bf16(const void* x, void* y, int64_t n, void* stream);
 /* Sinusoidal timestep projection (256 ch, flip_sin_to_cos, shift 0) -> bf16 [n,256];
  * t is fp32 [n] ALREADY multiplied by timestep_scale_multiplier.
  * ltx_video/models/transformers/embeddings.py:10-50 as used by AdaLayerNormSingle. */
 int ltxmi_timestep_embedding_bf16(const float* t, void* out, int32_t n, int32_t dim, void* stream);
 /* STG "attention values" blend: a = a*m[b] + v*(1-m[b]),  attention.py:1134-1141.
- * a: [B, L, D] contiguous rows lda; v rows ldv; m fp32 [B]. */
+ * a: [B, L, D] contiguous rows lda; v rows ldv; m fp32 [B].  D, lda, ldv % 8 == 0, a and v 16-byte aligned (else
+ * LTXMI_ERR_UNSUPPORTED and nothing is written).  Rows with m[b] == 1 are not touched. */
 int ltxmi_stg_blend_bf16(void* a, int64_t lda, const void* v, int64_t ldv,
                          const float* m, int32_t B, int32_t L, int32_t D, void* stream);
 /* The same blend (attention.py:1127-1141) over a contiguous a [G, B, L, D] with v addressed by strides in elements:
@@ -451,7 +453,8 @@ int ltxmi_pixelnorm_ada_silu_bf16(const void* x, void* y, int64_t rows, int32_t 
                                   int64_t rows_per_batch, const float* scale, const float* shift,
                                   int32_t apply_silu, float eps, void* stream);
 
-/* y = a + b elementwise (ResnetBlock3D skip add, causal_video_autoencoder.py:1256). */
+/* y = a + b elementwise (ResnetBlock3D skip add, causal_video_autoencoder.py:1256).  a, b, y dense; n % 8 == 0, all three
+ * 16-byte aligned (else LTXMI_ERR_UNSUPPORTED and nothing is written).  y may be a or b. */
 int ltxmi_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream);
 
 /* Channel LayerNorm with affine over NDHWC rows (norm3 of res_x_y blocks,
@@ -498,6 +501,8 @@ int ltxmi_ndhwc_to_ncdhw_bf16(const void* x, int64_t ldx, int32_t c0, void* y, i
  * pipeline_ltx_video.py:1035-1051); latents: [n], fp32 (latents_bf16 = 0) or bf16 (= 1).
  * workspace: >= LTXMI_GUIDANCE_WORKSPACE_FLOATS floats (per-block partial sums: the reductions use no
  * atomics, so the step is run-to-run deterministic); contents need not be initialised.
+ * The two standard deviations of the rescale are sums of squares about the data (text about its mean, the guided
+ * prediction about a value near its mean), in fp32: a prediction whose mean is many deviations keeps them.
  * ------------------------------------------------------------------------------- */
 #define LTXMI_GUIDANCE_WORKSPACE_FLOATS 2048
 int ltxmi_guidance_step_bf16(const void* noise_pred, int64_t n, int32_t num_conds,
@@ -510,7 +515,8 @@ int ltxmi_guidance_step_bf16(const void* noise_pred, int64_t n, int32_t num_cond
  * denoising_step, pipeline_ltx_video.py:1309-1342 -- token i (of `channels` values each) is
  * advanced only if t - 1e-6 < 1 - cond_mask[i]; hard-conditioned tokens (mask 1) never move.
  * cond_mask: fp32 [n / channels] or NULL (= ltxmi_guidance_step_bf16).  For the tokens that do
- * move, their per-token timestep min(t, 1 - mask) equals t, so dt is the global step. */
+ * move, their per-token timestep min(t, 1 - mask) equals t (to within 1e-6, for a token whose 1 - mask lies within 1e-6
+ * below t), so dt is the global step.  The comparison is made in fp32, as the reference makes it. */
 int ltxmi_guidance_step_masked_bf16(const void* noise_pred, int64_t n, int32_t num_conds,
                                     float guidance_scale, float stg_scale, float rescaling_scale,
                                     int32_t do_cfg, int32_t do_stg, int32_t do_rescale,

@@ -221,7 +221,11 @@ __global__ void unpatchify4_kernel(const uint16_t* __restrict__ x, uint16_t* __r
 }
 
 // ---------------------------------------------------------------- guidance + Euler step
-// pass 1 sums: text*uncond, uncond^2, text, text^2; pass 2 sums: out, out^2 (per-block partials in the workspace)
+// pass 1 sums: text*uncond, uncond^2, text; pass 2 sums: (text - mean)^2, out - shift, (out - shift)^2 (per-block partials
+// in the workspace).  The two standard deviations of the rescale are taken about the data, not as E[x^2] - mean^2: text
+// about its mean from pass 1, out about the guidance formula applied to that mean (near out's mean when the three
+// predictions have similar means, and a shift only: the variance formula below is exact for any value of it).  In fp32
+// the one-pass form lost mean^2 / variance ulps, 3e-6 of the factor on data with mean 4 and deviation 0.5.
 struct GuidanceP {
     const uint16_t* np; int64_t n; int num_conds;
     float gs, stg, rs; int do_cfg, do_stg, do_rescale;
@@ -231,9 +235,9 @@ struct GuidanceP {
 
 // Deterministic two-level sums (no atomics: run-to-run identical latents): every block writes its partial
 // to part[block][NV]; the consumer kernel adds the partials of all blocks in block order.
-// Workspace layout (floats): [8 .. 8 + 4*256) partials of pass 1, [1032 .. 1032 + 2*256) partials of pass 2.
+// Workspace layout (floats): [8 .. 8 + 3*256) partials of pass 1, [776 .. 776 + 3*256) partials of pass 2.
 constexpr int GD_MAX_BLOCKS = 256;
-constexpr int GD_PART1 = 8, GD_PART2 = 8 + 4 * GD_MAX_BLOCKS;
+constexpr int GD_PART1 = 8, GD_PART2 = 8 + 3 * GD_MAX_BLOCKS;
 template <int NV>
 __device__ __forceinline__ void block_partial_store(float (&v)[NV], float* part) {
     __shared__ float red[NV][PW_THREADS / 64];
@@ -283,41 +287,44 @@ __device__ __forceinline__ float guidance_combine(const GuidanceP& p, float unc,
 }
 
 __global__ void guidance_reduce1(GuidanceP p) {
-    float a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+    float a0 = 0, a1 = 0, a2 = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * blockDim.x) {
         float u, t, q;
         guidance_fetch(p, i, u, t, q);
-        a0 += t * u; a1 += u * u; a2 += t; a3 += t * t;
+        a0 += t * u; a1 += u * u; a2 += t;
     }
-    float acc[4] = {a0, a1, a2, a3};
+    float acc[3] = {a0, a1, a2};
     block_partial_store(acc, p.ws + GD_PART1);
 }
 
 __global__ void guidance_reduce2(GuidanceP p) {
-    float s1[4];
+    float s1[3];
     sum_partials(p.ws + GD_PART1, gridDim.x, s1);
     const float alpha = s1[0] / (s1[1] + 1e-8f);
-    float a4 = 0, a5 = 0;
+    const float mean_t = s1[2] / (float)p.n;
+    const float shift_o = guidance_combine(p, mean_t, mean_t, mean_t, alpha);
+    float a3 = 0, a4 = 0, a5 = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * blockDim.x) {
         float u, t, q;
         guidance_fetch(p, i, u, t, q);
-        const float o = guidance_combine(p, u, t, q, alpha);
-        a4 += o; a5 += o * o;
+        const float d = t - mean_t, e = guidance_combine(p, u, t, q, alpha) - shift_o;
+        a3 += d * d; a4 += e; a5 += e * e;
     }
-    float acc[2] = {a4, a5};
+    float acc[3] = {a3, a4, a5};
     block_partial_store(acc, p.ws + GD_PART2);
 }
 
 __global__ void guidance_apply(GuidanceP p) {
-    float s1[4], s2[2];
+    float s1[3], s2[3];
     sum_partials(p.ws + GD_PART1, gridDim.x, s1);
     sum_partials(p.ws + GD_PART2, gridDim.x, s2);
     const float alpha = s1[0] / (s1[1] + 1e-8f);
     float factor = 1.f;
     if (p.do_stg && p.do_rescale && p.stg > 0.f) {
         const float n = (float)p.n;
-        const float var_t = fmaxf((s1[3] - s1[2] * s1[2] / n) / (n - 1.f), 0.f);   // torch .std(): unbiased
-        const float var_o = fmaxf((s2[1] - s2[0] * s2[0] / n) / (n - 1.f), 0.f);
+        // torch .std(): unbiased.  text is centred on its fp32 mean, whose own error adds 1e-12 (mean / deviation)^2 at most
+        const float var_t = s2[0] / (n - 1.f);
+        const float var_o = fmaxf((s2[2] - s2[1] * s2[1] / n) / (n - 1.f), 0.f);
         factor = p.rs * (sqrtf(var_t) / sqrtf(var_o)) + (1.f - p.rs);
     }
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -351,6 +358,7 @@ using namespace ltxmi;
 extern "C" int ltxmi_silu_bf16(const void* x, void* y, int64_t n, void* stream) {
     LTXMI_REQUIRE(x && y, LTXMI_ERR_INVALID_ARG, "ltxmi_silu_bf16: NULL argument");
     LTXMI_REQUIRE(n > 0 && n % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_silu_bf16: n=%lld must be a positive multiple of 8", (long long)n);
+    LTXMI_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_silu_bf16: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(silu_kernel, dim3(pw_grid(n / 8)), dim3(PW_THREADS), 0, (hipStream_t)stream,
                        (const uint16_t*)x, (uint16_t*)y, n / 8);
     return check_launch("ltxmi_silu_bf16");
@@ -359,6 +367,8 @@ extern "C" int ltxmi_silu_bf16(const void* x, void* y, int64_t n, void* stream) 
 extern "C" int ltxmi_add_bf16(const void* a, const void* b, void* y, int64_t n, void* stream) {
     LTXMI_REQUIRE(a && b && y, LTXMI_ERR_INVALID_ARG, "ltxmi_add_bf16: NULL argument");
     LTXMI_REQUIRE(n > 0 && n % 8 == 0, LTXMI_ERR_UNSUPPORTED, "ltxmi_add_bf16: n=%lld must be a positive multiple of 8", (long long)n);
+    LTXMI_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
+                  "ltxmi_add_bf16: pointers must be 16-byte aligned");
     hipLaunchKernelGGL(add_kernel, dim3(pw_grid(n / 8)), dim3(PW_THREADS), 0, (hipStream_t)stream,
                        (const uint16_t*)a, (const uint16_t*)b, (uint16_t*)y, n / 8);
     return check_launch("ltxmi_add_bf16");
@@ -378,8 +388,8 @@ extern "C" int ltxmi_stg_blend_bf16(void* a, int64_t lda, const void* v, int64_t
                                     int32_t L, int32_t D, void* stream) {
     LTXMI_REQUIRE(a && v && m, LTXMI_ERR_INVALID_ARG, "ltxmi_stg_blend_bf16: NULL argument");
     LTXMI_REQUIRE(B > 0 && L > 0 && D > 0, LTXMI_ERR_INVALID_ARG, "ltxmi_stg_blend_bf16: non-positive size");
-    LTXMI_REQUIRE(D % 8 == 0 && lda % 8 == 0 && ldv % 8 == 0, LTXMI_ERR_UNSUPPORTED,
-                  "ltxmi_stg_blend_bf16: D and strides must be multiples of 8");
+    LTXMI_REQUIRE(D % 8 == 0 && lda % 8 == 0 && ldv % 8 == 0 && (((uintptr_t)a | (uintptr_t)v) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
+                  "ltxmi_stg_blend_bf16: D and strides must be multiples of 8, pointers 16-byte aligned");
     const int64_t total = (int64_t)B * L * (D / 8);
     hipLaunchKernelGGL(stg_blend_kernel, dim3(pw_grid(total)), dim3(PW_THREADS), 0, (hipStream_t)stream, (uint16_t*)a,
                        lda, (const uint16_t*)v, ldv, m, L, D, total);

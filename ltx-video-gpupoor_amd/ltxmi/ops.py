@@ -464,6 +464,8 @@ def stg_blend_grouped_(a, v, m_f32):
 
 def silu(x, out=None):
     _chk_bf16(x, out)
+    if not x.is_contiguous() or (out is not None and (not out.is_contiguous() or out.shape != x.shape)):
+        raise ValueError("ltxmi.silu: x / out must be contiguous and equally shaped")
     out = torch.empty_like(x) if out is None else out
     check(lib.ltxmi_silu_bf16(_ptr(x), _ptr(out), x.numel(), _stream()), "ltxmi_silu_bf16")
     return out
@@ -471,6 +473,9 @@ def silu(x, out=None):
 
 def add(a, b, out=None):
     _chk_bf16(a, b, out)
+    if not a.is_contiguous() or not b.is_contiguous() or b.shape != a.shape or \
+            (out is not None and (not out.is_contiguous() or out.shape != a.shape)):
+        raise ValueError("ltxmi.add: a / b / out must be contiguous and equally shaped")
     out = torch.empty_like(a) if out is None else out
     check(lib.ltxmi_add_bf16(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "ltxmi_add_bf16")
     return out
@@ -694,7 +699,9 @@ def ncdhw_to_ndhwc(z, std=None, mean=None):
 
 def unpatchify_to_ncdhw(x, c_out, patch):
     _chk_bf16(x)
-    B, T, H, W, _ = x.shape
+    B, T, H, W, Cp = x.shape
+    if not x.is_contiguous() or Cp != c_out * patch * patch:
+        raise ValueError(f"ltxmi.unpatchify_to_ncdhw: x must be contiguous with {c_out * patch * patch} channels")
     out = torch.empty((B, c_out, T, H * patch, W * patch), dtype=BF16, device=x.device)
     check(lib.ltxmi_unpatchify_to_ncdhw_bf16(_ptr(x), _ptr(out), B, T, H, W, c_out, patch, _stream()),
           "ltxmi_unpatchify_to_ncdhw_bf16")
