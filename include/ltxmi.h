@@ -524,6 +524,27 @@ int ltxmi_guidance_step_masked_bf16(const void* noise_pred, int64_t n, int32_t n
                                     const float* cond_mask, int32_t channels, float t,
                                     float* workspace, void* stream);
 
+/* The same step for `batch` videos of one pipeline call, in three launches whatever `batch` is (grid: blocks x batch).
+ * noise_pred: bf16 [num_conds][batch][n], chunk-major -- what the transformer returns for the row order
+ *             [uncond x batch, text x batch, perturbed x batch] (pipeline_ltx_video.py:1035-1051, 1184-1188).
+ * latents:    [batch][n], fp32 or bf16.   cond_mask: fp32 [batch][n / channels] or NULL.
+ * workspace:  >= batch * LTXMI_GUIDANCE_WORKSPACE_FLOATS floats, `workspace_floats` of them; contents need not be initialised.
+ * Every video has its own sums: its own CFG-star alpha, text mean, two deviations, rescale factor and mask test (the
+ * dim=1 sums of :1192-1198 and :1212-1217 per sample, as they are at batch 1; the reference's own broadcast of them is
+ * only well-formed for one sample).  A video's block partials are added in block order, no atomics.
+ * BIT CONTRACT: for every video j the result equals, bit for bit, ltxmi_guidance_step_masked_bf16 on noise_pred[:, j],
+ * latents[j], cond_mask[j]: the one-sample entries run the same kernels with batch = 1, and a thread accumulates the same
+ * elements of its video in the same order at every batch.  All offsets are 64-bit.
+ * LTXMI_ERR_INVALID_ARG (before any launch, the message names the argument): a NULL noise_pred / latents / workspace,
+ * batch outside 1..65535, n <= 1, num_conds inconsistent with do_cfg / do_stg, a mask with channels <= 0 or
+ * n % channels != 0, workspace_floats < batch * LTXMI_GUIDANCE_WORKSPACE_FLOATS. */
+int ltxmi_guidance_step_batched_bf16(const void* noise_pred, int32_t batch, int64_t n, int32_t num_conds,
+                                     float guidance_scale, float stg_scale, float rescaling_scale,
+                                     int32_t do_cfg, int32_t do_stg, int32_t do_rescale,
+                                     void* latents, int32_t latents_bf16, float dt,
+                                     const float* cond_mask, int32_t channels, float t,
+                                     float* workspace, int64_t workspace_floats, void* stream);
+
 /* add_noise_to_image_conditioning_latents, pipeline_ltx_video.py:606-629: tokens with
  * cond_mask > 1 - 1e-6 become init_latents + noise_scale * noise * t^2, others are untouched.
  * latents / init_latents / noise: [tokens, channels], all fp32 (is_bf16 = 0) or all bf16 (= 1). */

@@ -228,6 +228,8 @@ __global__ void unpatchify4_kernel(const uint16_t* __restrict__ x, uint16_t* __r
 // the one-pass form lost mean^2 / variance ulps, 3e-6 of the factor on data with mean 4 and deviation 0.5.
 struct GuidanceP {
     const uint16_t* np; int64_t n; int num_conds;
+    int64_t chunk_stride;                                // elements between two chunks of noise_pred: batch * n
+    int64_t mask_stride;                                 // mask values per video: n / channels
     float gs, stg, rs; int do_cfg, do_stg, do_rescale;
     float* lat_f32; uint16_t* lat_bf16; float dt; float* ws;
     const float* cond_mask; int channels; float t;      // conditioning: token n steps iff t - 1e-6 < 1 - cond_mask[n]
@@ -238,6 +240,21 @@ struct GuidanceP {
 // Workspace layout (floats): [8 .. 8 + 3*256) partials of pass 1, [776 .. 776 + 3*256) partials of pass 2.
 constexpr int GD_MAX_BLOCKS = 256;
 constexpr int GD_PART1 = 8, GD_PART2 = 8 + 3 * GD_MAX_BLOCKS;
+constexpr int GD_WORKSPACE = 2048;                       // LTXMI_GUIDANCE_WORKSPACE_FLOATS: one video's share
+static_assert(GD_PART2 + 3 * GD_MAX_BLOCKS <= GD_WORKSPACE, "the partials of both passes fit one video's workspace");
+
+// The parameters as video blockIdx.y of the batch sees them: its [n] slice of every chunk, its latents, its mask row and its
+// own share of the workspace.  Everything below indexes within one video, so a video's threads add the same elements in
+// the same order whatever the batch is (at batch 1 the offsets are zero and chunk_stride is n: the one-sample step).
+__device__ __forceinline__ GuidanceP guidance_video(GuidanceP p) {
+    const int64_t v = blockIdx.y;
+    p.np += v * p.n;
+    if (p.lat_f32) p.lat_f32 += v * p.n;
+    if (p.lat_bf16) p.lat_bf16 += v * p.n;
+    if (p.cond_mask) p.cond_mask += v * p.mask_stride;
+    p.ws += v * GD_WORKSPACE;
+    return p;
+}
 template <int NV>
 __device__ __forceinline__ void block_partial_store(float (&v)[NV], float* part) {
     __shared__ float red[NV][PW_THREADS / 64];
@@ -271,9 +288,9 @@ __device__ __forceinline__ void guidance_fetch(const GuidanceP& p, int64_t i, fl
     // chunk order is (uncond, text, perturbed): pipeline_ltx_video.py:1035-1051
     int c = 0;
     unc = txt = ptb = 0.f;
-    if (p.do_cfg) unc = bf2f(p.np[(int64_t)(c++) * p.n + i]);
-    txt = bf2f(p.np[(int64_t)(c++) * p.n + i]);
-    if (p.do_stg) ptb = bf2f(p.np[(int64_t)(c++) * p.n + i]);
+    if (p.do_cfg) unc = bf2f(p.np[(int64_t)(c++) * p.chunk_stride + i]);
+    txt = bf2f(p.np[(int64_t)(c++) * p.chunk_stride + i]);
+    if (p.do_stg) ptb = bf2f(p.np[(int64_t)(c++) * p.chunk_stride + i]);
 }
 
 __device__ __forceinline__ float guidance_combine(const GuidanceP& p, float unc, float txt, float ptb, float alpha) {
@@ -286,7 +303,8 @@ __device__ __forceinline__ float guidance_combine(const GuidanceP& p, float unc,
     return out;
 }
 
-__global__ void guidance_reduce1(GuidanceP p) {
+__global__ void guidance_reduce1(GuidanceP all) {
+    const GuidanceP p = guidance_video(all);
     float a0 = 0, a1 = 0, a2 = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p.n; i += (int64_t)gridDim.x * blockDim.x) {
         float u, t, q;
@@ -297,7 +315,8 @@ __global__ void guidance_reduce1(GuidanceP p) {
     block_partial_store(acc, p.ws + GD_PART1);
 }
 
-__global__ void guidance_reduce2(GuidanceP p) {
+__global__ void guidance_reduce2(GuidanceP all) {
+    const GuidanceP p = guidance_video(all);
     float s1[3];
     sum_partials(p.ws + GD_PART1, gridDim.x, s1);
     const float alpha = s1[0] / (s1[1] + 1e-8f);
@@ -314,7 +333,8 @@ __global__ void guidance_reduce2(GuidanceP p) {
     block_partial_store(acc, p.ws + GD_PART2);
 }
 
-__global__ void guidance_apply(GuidanceP p) {
+__global__ void guidance_apply(GuidanceP all) {
+    const GuidanceP p = guidance_video(all);
     float s1[3], s2[3];
     sum_partials(p.ws + GD_PART1, gridDim.x, s1);
     sum_partials(p.ws + GD_PART2, gridDim.x, s2);
@@ -439,6 +459,30 @@ extern "C" int ltxmi_unpatchify_to_ncdhw_bf16(const void* x, void* y, int32_t B,
     return check_launch("ltxmi_unpatchify_to_ncdhw_bf16");
 }
 
+// The three launches of a step over `batch` videos, arguments already checked: grid (blocks, batch), a video per grid row.
+static void guidance_launch(const void* noise_pred, int32_t batch, int64_t n, int32_t num_conds, float guidance_scale,
+                            float stg_scale, float rescaling_scale, int32_t do_cfg, int32_t do_stg, int32_t do_rescale,
+                            void* latents, int32_t latents_bf16, float dt, const float* cond_mask, int32_t channels, float t,
+                            float* workspace, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    GuidanceP p;
+    p.np = (const uint16_t*)noise_pred; p.n = n; p.num_conds = num_conds;
+    p.chunk_stride = (int64_t)batch * n;
+    p.gs = guidance_scale; p.stg = stg_scale; p.rs = rescaling_scale;
+    p.do_cfg = do_cfg; p.do_stg = do_stg; p.do_rescale = do_rescale;
+    p.lat_f32 = latents_bf16 ? nullptr : (float*)latents;
+    p.lat_bf16 = latents_bf16 ? (uint16_t*)latents : nullptr;
+    p.dt = dt; p.ws = workspace;
+    p.cond_mask = cond_mask; p.channels = channels > 0 ? channels : 1; p.t = t;
+    p.mask_stride = n / p.channels;
+    unsigned g = pw_grid(n);
+    if (g > 256) g = 256;
+    const dim3 grid(g, (unsigned)batch);
+    hipLaunchKernelGGL(guidance_reduce1, grid, dim3(PW_THREADS), 0, s, p);
+    hipLaunchKernelGGL(guidance_reduce2, grid, dim3(PW_THREADS), 0, s, p);
+    hipLaunchKernelGGL(guidance_apply, grid, dim3(PW_THREADS), 0, s, p);
+}
+
 extern "C" int ltxmi_guidance_step_masked_bf16(const void* noise_pred, int64_t n, int32_t num_conds,
                                                float guidance_scale, float stg_scale, float rescaling_scale,
                                                int32_t do_cfg, int32_t do_stg, int32_t do_rescale, void* latents,
@@ -448,23 +492,36 @@ extern "C" int ltxmi_guidance_step_masked_bf16(const void* noise_pred, int64_t n
     LTXMI_REQUIRE(n > 1, LTXMI_ERR_INVALID_ARG, "ltxmi_guidance_step_bf16: n must be > 1");
     LTXMI_REQUIRE(num_conds == 1 + (do_cfg ? 1 : 0) + (do_stg ? 1 : 0), LTXMI_ERR_INVALID_ARG,
                   "ltxmi_guidance_step_bf16: num_conds=%d inconsistent with do_cfg=%d do_stg=%d", num_conds, do_cfg, do_stg);
-    hipStream_t s = (hipStream_t)stream;
-    GuidanceP p;
-    p.np = (const uint16_t*)noise_pred; p.n = n; p.num_conds = num_conds;
-    p.gs = guidance_scale; p.stg = stg_scale; p.rs = rescaling_scale;
-    p.do_cfg = do_cfg; p.do_stg = do_stg; p.do_rescale = do_rescale;
-    p.lat_f32 = latents_bf16 ? nullptr : (float*)latents;
-    p.lat_bf16 = latents_bf16 ? (uint16_t*)latents : nullptr;
-    p.dt = dt; p.ws = workspace;
-    p.cond_mask = cond_mask; p.channels = channels > 0 ? channels : 1; p.t = t;
     LTXMI_REQUIRE(!cond_mask || (channels > 0 && n % channels == 0), LTXMI_ERR_INVALID_ARG,
                   "ltxmi_guidance_step_bf16: n=%lld is not a multiple of channels=%d", (long long)n, channels);
-    unsigned g = pw_grid(n);
-    if (g > 256) g = 256;
-    hipLaunchKernelGGL(guidance_reduce1, dim3(g), dim3(PW_THREADS), 0, s, p);
-    hipLaunchKernelGGL(guidance_reduce2, dim3(g), dim3(PW_THREADS), 0, s, p);
-    hipLaunchKernelGGL(guidance_apply, dim3(g), dim3(PW_THREADS), 0, s, p);
+    guidance_launch(noise_pred, 1, n, num_conds, guidance_scale, stg_scale, rescaling_scale, do_cfg, do_stg, do_rescale,
+                    latents, latents_bf16, dt, cond_mask, channels, t, workspace, stream);
     return check_launch("ltxmi_guidance_step_bf16");
+}
+
+extern "C" int ltxmi_guidance_step_batched_bf16(const void* noise_pred, int32_t batch, int64_t n, int32_t num_conds,
+                                                float guidance_scale, float stg_scale, float rescaling_scale,
+                                                int32_t do_cfg, int32_t do_stg, int32_t do_rescale, void* latents,
+                                                int32_t latents_bf16, float dt, const float* cond_mask,
+                                                int32_t channels, float t, float* workspace, int64_t workspace_floats,
+                                                void* stream) {
+    LTXMI_REQUIRE(noise_pred, LTXMI_ERR_INVALID_ARG, "ltxmi_guidance_step_batched_bf16: noise_pred is NULL");
+    LTXMI_REQUIRE(latents, LTXMI_ERR_INVALID_ARG, "ltxmi_guidance_step_batched_bf16: latents is NULL");
+    LTXMI_REQUIRE(workspace, LTXMI_ERR_INVALID_ARG, "ltxmi_guidance_step_batched_bf16: workspace is NULL");
+    LTXMI_REQUIRE(batch >= 1 && batch <= 65535, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_guidance_step_batched_bf16: batch=%d must be in 1..65535 (one grid row per video)", batch);
+    LTXMI_REQUIRE(n > 1, LTXMI_ERR_INVALID_ARG, "ltxmi_guidance_step_batched_bf16: n=%lld must be > 1", (long long)n);
+    LTXMI_REQUIRE(num_conds == 1 + (do_cfg ? 1 : 0) + (do_stg ? 1 : 0), LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_guidance_step_batched_bf16: num_conds=%d inconsistent with do_cfg=%d do_stg=%d", num_conds, do_cfg,
+                  do_stg);
+    LTXMI_REQUIRE(!cond_mask || (channels > 0 && n % channels == 0), LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_guidance_step_batched_bf16: cond_mask needs channels=%d > 0 dividing n=%lld", channels, (long long)n);
+    LTXMI_REQUIRE(workspace_floats >= (int64_t)batch * GD_WORKSPACE, LTXMI_ERR_INVALID_ARG,
+                  "ltxmi_guidance_step_batched_bf16: workspace_floats=%lld is short of batch * %d = %lld",
+                  (long long)workspace_floats, GD_WORKSPACE, (long long)batch * GD_WORKSPACE);
+    guidance_launch(noise_pred, batch, n, num_conds, guidance_scale, stg_scale, rescaling_scale, do_cfg, do_stg, do_rescale,
+                    latents, latents_bf16, dt, cond_mask, channels, t, workspace, stream);
+    return check_launch("ltxmi_guidance_step_batched_bf16");
 }
 
 extern "C" int ltxmi_guidance_step_bf16(const void* noise_pred, int64_t n, int32_t num_conds, float guidance_scale,

@@ -119,6 +119,9 @@ SIGNATURES = {
     "ltxmi_guidance_step_masked_bf16": (c_int, [c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_int,
                                                 c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_float, c_void_p,
                                                 c_void_p]),
+    "ltxmi_guidance_step_batched_bf16": (c_int, [c_void_p, c_int, c_int64, c_int, c_float, c_float, c_float, c_int, c_int,
+                                                 c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_float, c_void_p,
+                                                 c_int64, c_void_p]),
     "ltxmi_image_cond_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_float,
                                        c_float, c_void_p]),
     "ltxmi_groupnorm_silu_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,

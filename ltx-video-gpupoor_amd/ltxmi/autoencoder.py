@@ -880,12 +880,29 @@ def un_normalize_latents(latents, vae, vae_per_channel_normalize: bool = False):
     return latents / _scaling_factor(vae)
 
 
+def randn_rows(shape, generator=None, device=None, dtype=None, randn=None):
+    """``torch.randn(shape)`` by the semantics of diffusers' ``randn_tensor``: a list of ``shape[0]`` generators draws row j
+    from generator j, at the shape (1, *shape[1:]) a call of its own with that generator would draw -- so row j of a batch
+    is what the single call gets.  One generator (or None: the global RNG) draws the whole batch at once.  ``randn``: the
+    caller's ``torch.randn`` (the one helper for every draw of the pipeline)."""
+    randn = torch.randn if randn is None else randn
+    if not isinstance(generator, (list, tuple)):
+        return randn(tuple(shape), generator=generator, device=device, dtype=dtype)
+    if len(generator) != shape[0]:
+        raise ValueError(f"ltxmi: {len(generator)} generators for a batch of {shape[0]}")
+    one = (1, *tuple(shape)[1:])
+    return torch.cat([randn(one, generator=g, device=device, dtype=dtype) for g in generator], dim=0)
+
+
 def vae_encode(media_items, vae: CausalVideoAutoencoder, split_size: int = 1, vae_per_channel_normalize=False,
-               generator: Optional[torch.Generator] = None, sample_posterior: bool = True):
+               generator: Optional[torch.Generator] = None, sample_posterior: bool = True,
+               num_samples: Optional[int] = None):
     """vae_encode.py:22-91: pixels [B,3,F,H,W] (or [B,3,H,W]) in [-1,1] -> normalised latents [B,C,f,h,w].
     ``latent_dist.sample()`` as there (``sample_posterior=False`` takes the mode).  The per-channel
     normalisation commutes with the sampling as (mean - m)/s + (std/s) * noise; it is folded into the
-    encoder's layout pass for the mean and applied to the noise term here."""
+    encoder's layout pass for the mean and applied to the noise term here.
+    ``num_samples`` (extension): one media item shared by that many videos of a call -- encoded once, the posterior sampled
+    once per video (``generator`` may be a list with one generator per video, see ``randn_rows``)."""
     if media_items.dim() == 4:
         media_items = media_items.unsqueeze(2)
     if media_items.shape[1] != 3:
@@ -898,8 +915,12 @@ def vae_encode(media_items, vae: CausalVideoAutoencoder, split_size: int = 1, va
     dist = vae.encode(media_items.to(vae.dtype), _stats=stats).latent_dist
     scale = 1.0 if vae_per_channel_normalize else float(vae._config.get("scaling_factor", 1.0))
     z = dist.mean.float() * scale
+    if num_samples is not None and num_samples != z.shape[0]:
+        if z.shape[0] != 1:
+            raise ValueError(f"ltxmi.vae_encode: {z.shape[0]} media items for {num_samples} videos (one each, or one for all)")
+        z = z.expand(num_samples, *z.shape[1:])
     if sample_posterior and not dist.deterministic:
-        noise = torch.randn(z.shape, generator=generator, device=z.device, dtype=torch.float32)
+        noise = randn_rows(z.shape, generator, z.device, torch.float32)
         s = dist.std * scale
         if stats is not None:
             s = s / stats[0].view(1, -1, 1, 1, 1)

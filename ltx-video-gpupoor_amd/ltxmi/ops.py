@@ -793,8 +793,40 @@ def guidance_step_(noise_pred, latents, dt, guidance_scale, stg_scale, rescaling
     return latents
 
 
+def guidance_step_batched_(noise_pred, latents, dt, guidance_scale, stg_scale, rescaling_scale, do_cfg, do_stg, do_rescale,
+                           workspace, cond_mask=None, t=0.0):
+    """The step for b videos of one call: noise_pred bf16 [num_conds * b, N, C] in chunk order (uncond x b, text x b,
+    perturbed x b); latents fp32/bf16 [b, N, C], updated in place; cond_mask fp32 [b, N] (or None); workspace fp32 of at
+    least b * GUIDANCE_WORKSPACE_FLOATS values.  Video j gets the bits ``guidance_step_`` gives for noise_pred[j::b],
+    latents[j:j + 1], cond_mask[j:j + 1]: every sum of the guidance is per video."""
+    _chk_bf16(noise_pred)
+    is_bf16 = latents.dtype == BF16
+    if not is_bf16 and latents.dtype != torch.float32:
+        raise TypeError("ltxmi.guidance_step_batched_: latents must be fp32 or bf16")
+    b = latents.shape[0]
+    if latents.dim() != 3 or noise_pred.dim() != 3 or not noise_pred.is_contiguous() or noise_pred.shape[0] % b != 0:
+        raise ValueError("ltxmi.guidance_step_batched_: noise_pred must be contiguous [num_conds * b, N, C] for latents [b, N, C]")
+    num_conds = noise_pred.shape[0] // b
+    n = noise_pred[0].numel()
+    if not latents.is_contiguous() or latents.numel() != b * n:
+        raise ValueError("ltxmi.guidance_step_batched_: latents must be contiguous and match one chunk of noise_pred")
+    if workspace.dtype != torch.float32 or workspace.numel() < b * GUIDANCE_WORKSPACE_FLOATS:
+        raise ValueError(f"ltxmi.guidance_step_batched_: workspace must hold {b} x {GUIDANCE_WORKSPACE_FLOATS} fp32 values")
+    C = noise_pred.shape[-1]
+    if cond_mask is not None and (cond_mask.dtype != torch.float32 or not cond_mask.is_contiguous()
+                                  or cond_mask.numel() * C != b * n):
+        raise ValueError("ltxmi.guidance_step_batched_: cond_mask must be contiguous fp32 with one value per token")
+    check(lib.ltxmi_guidance_step_batched_bf16(_ptr(noise_pred), b, n, num_conds, guidance_scale, stg_scale,
+                                               rescaling_scale, int(do_cfg), int(do_stg), int(do_rescale),
+                                               _ptr(latents), int(is_bf16), float(dt),
+                                               None if cond_mask is None else _ptr(cond_mask), C, float(t),
+                                               _ptr(workspace), workspace.numel(), _stream()),
+          "ltxmi_guidance_step_batched_bf16")
+    return latents
+
+
 def image_cond_noise_(latents, init_latents, noise, cond_mask, noise_scale, t):
-    """latents/init_latents/noise [1, N, C] (all fp32 or all bf16), cond_mask fp32 [1, N]; in place."""
+    """latents/init_latents/noise [b, N, C] (all fp32 or all bf16), cond_mask fp32 [b, N]; in place."""
     is_bf16 = latents.dtype == BF16
     for x in (latents, init_latents, noise):
         if x.dtype != latents.dtype or x.shape != latents.shape or not x.is_contiguous():

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .attention import SkipLayerStrategy
-from .autoencoder import vae_decode, vae_encode
+from .autoencoder import randn_rows, vae_decode, vae_encode
 from .patchifier import SymmetricPatchifier, latent_to_pixel_coords_from_factors
 
 
@@ -45,6 +45,11 @@ def _refuse(rows):
 
 def _shape(x):
     return None if x is None else tuple(x.shape)
+
+
+def _randn(shape, generator, device, dtype):
+    """Every draw of the pipeline: ``randn_rows`` (a generator list gives video j what its single call draws)."""
+    return randn_rows(shape, generator, device, dtype, randn=torch.randn)
 
 
 def _resize_frames(video, height, width):
@@ -188,20 +193,24 @@ class LTXVideoPipeline:
         """pipeline_ltx_video.py:632-710: (b, c, f, h, w) latents = pure noise, or the given latents / the encoded
         ``media_items`` noised to ``timestep``.  The noise is drawn in PATCHIFIED order (b, f*h*w, c) (:696-699)."""
         batch, channels, frames, rows, cols = latent_shape
-        if isinstance(generator, list) and len(generator) != batch:
+        if isinstance(generator, (list, tuple)) and len(generator) != batch:
             raise ValueError(f"ltxmi.LTXVideoPipeline: {len(generator)} generators for a batch of {batch}")
         assert latents is None or media_items is None, "ltxmi.LTXVideoPipeline: latents and media_items are alternatives"
         assert (latents is None and media_items is None) or timestep < 1.0, \
             "ltxmi.LTXVideoPipeline: at timestep 1 the given latents / media_items would be all noise (pass strength < 1)"
         start = latents
         if media_items is not None:
+            if media_items.shape[0] not in (1, batch):
+                raise ValueError(f"ltxmi.LTXVideoPipeline: media_items holds {media_items.shape[0]} videos for a batch of "
+                                 f"{batch} (one per video, or one shared by all)")
             start = vae_encode(media_items.to(dtype=self.vae.dtype, device=self.vae.device), self.vae,
                                vae_per_channel_normalize=vae_per_channel_normalize)
+            start = start.expand(batch, *start.shape[1:])
         if start is not None:
             assert tuple(start.shape) == tuple(latent_shape), \
                 f"ltxmi.LTXVideoPipeline: latents {tuple(start.shape)} where the call needs {tuple(latent_shape)}"
             start = start.to(device=device, dtype=dtype)
-        noise = torch.randn((batch, frames * rows * cols, channels), generator=generator, device=device, dtype=dtype)
+        noise = _randn((batch, frames * rows * cols, channels), generator, device, dtype)
         noise = self.patchifier.unpatchify(noise, rows, cols, channels) * self.scheduler.init_noise_sigma
         return noise if start is None else timestep * noise + (1 - timestep) * start
 
@@ -281,7 +290,9 @@ class LTXVideoPipeline:
     def prepare_conditioning(self, conditioning_items, init_latents, num_frames, height, width,
                              vae_per_channel_normalize=False, generator=None, sample_posterior=True):
         """:1344-1548.  init_latents (b, c, f_l, h_l, w_l) -> (latents (b, N, c), pixel_coords (b, 3, N),
-        conditioning_mask (b, N) fp32 or None, number of extra conditioning tokens in front)."""
+        conditioning_mask (b, N) fp32 or None, number of extra conditioning tokens in front).  A media item holds one
+        clip per video of the call or one shared by all (encoded once); every draw goes through ``_randn``."""
+        batch = init_latents.shape[0]
         extra_latents, extra_coords, extra_mask = [], [], []
         causal_fix = bool(getattr(self.transformer.config, "causal_temporal_positioning", True))
         init_mask = torch.zeros_like(init_latents[:, 0], dtype=torch.float32) if conditioning_items else None
@@ -295,9 +306,13 @@ class LTXVideoPipeline:
             assert n_frames % 8 == 1, f"a conditioning item has 8k + 1 frames, got {n_frames}"
             assert 0 <= frame_no <= num_frames - n_frames, \
                 f"frames {frame_no}..{frame_no + n_frames - 1} of a conditioning item lie outside the {num_frames}-frame video"
+            if media.shape[0] not in (1, batch):
+                raise ValueError(f"ltxmi.LTXVideoPipeline: a conditioning item holds {media.shape[0]} clips for a batch of "
+                                 f"{batch} (one per video, or one shared by all)")
             lat = vae_encode(media.to(dtype=self.vae.dtype, device=self.vae.device), self.vae,
                              vae_per_channel_normalize=vae_per_channel_normalize, generator=generator,
-                             sample_posterior=sample_posterior).to(dtype=init_latents.dtype)
+                             sample_posterior=sample_posterior, num_samples=batch).to(dtype=init_latents.dtype)
+            lat = lat.expand(batch, *lat.shape[1:])
             if frame_no == 0:                                          # written into the grid, at its place in the frame
                 lat, x, y = self._get_latent_spatial_position(lat, item, height, width, strip_latent_border=True)
                 f, y1, x1 = lat.shape[2], y + lat.shape[3], x + lat.shape[4]
@@ -308,7 +323,7 @@ class LTXVideoPipeline:
                 init_latents, init_mask, lat = self._handle_non_first_conditioning_sequence(
                     init_latents, init_mask, lat, frame_no, strength)
             if lat is not None:                                        # extra tokens in front, at the item's frames
-                noise = torch.randn(lat.shape, generator=generator, device=lat.device, dtype=lat.dtype)
+                noise = _randn(lat.shape, generator, lat.device, lat.dtype)
                 tokens, coords = self.patchifier.patchify(torch.lerp(noise, lat, strength))
                 coords = self._pixel_coords(coords, causal_fix)
                 coords[:, 0] += frame_no
@@ -357,7 +372,7 @@ class LTXVideoPipeline:
         return gs, stg, rs, skip_block_list
 
     @staticmethod
-    def _refuse_outside_this_path(prompt, prompt_embeds, is_video, offload_to_cpu, num_videos):
+    def _refuse_outside_this_path(prompt, prompt_embeds, is_video, offload_to_cpu):
         """What the reference's ``__call__`` takes and this one does not."""
         _refuse([(refused, NotImplementedError, message) for refused, message in [
             (prompt is not None or prompt_embeds is None,
@@ -365,9 +380,6 @@ class LTXVideoPipeline:
              "prompts go through encode_prompt / LTXMultiScalePipeline with the caller's T5"),
             (not is_video, "is_video=False (single images, video_scale_factor 1) is outside this path"),
             (offload_to_cpu, "offload_to_cpu is not on this path (everything is resident in HBM)"),
-            (num_videos != 1,
-             "one prompt and one video per call on this path (the reference's CFG-star broadcast at "
-             "pipeline_ltx_video.py:1199 is only well-formed for batch 1)"),
         ]])
 
     def _initial_latents(self, latents, media_items, timestep, latent_shape, dtype, device, generator,
@@ -376,7 +388,9 @@ class LTXVideoPipeline:
         if dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("ltxmi.LTXVideoPipeline: latents are kept in fp32 or bf16 (prompt_embeds' dtype by default)")
         if latents is not None and latents.dim() == 3:                                   # extension: given patchified noise
-            channels, _, rows, cols = latent_shape[1:]
+            batch, channels, frames, rows, cols = latent_shape
+            assert tuple(latents.shape) == (batch, frames * rows * cols, channels), \
+                f"ltxmi.LTXVideoPipeline: latents {tuple(latents.shape)} where the call needs {(batch, frames * rows * cols, channels)}"
             return self.patchifier.unpatchify(latents.to(device=device, dtype=dtype), rows, cols, channels)
         return self.prepare_latents(latents=latents, media_items=media_items, timestep=timestep, latent_shape=latent_shape,
                                     dtype=dtype, device=device, generator=generator,
@@ -386,9 +400,11 @@ class LTXVideoPipeline:
     def _stochastic_step_(noise_pred, latents, t, dt, guidance, cond_mask, one_minus_mask):
         """rf.py:368-373 behind the same guidance: x0 = x - t v by the fused kernel with dt = t on a copy (tokens the mask
         holds back stay as they are), then the re-noising to t - dt; the draw comes from the global RNG, as the
-        reference's torch.randn_like does.  ``guidance`` = ops.guidance_step_'s arguments after ``dt``."""
+        reference's torch.randn_like does (one draw for the whole batch: no per-video reproducibility is claimed).
+        ``guidance`` = ops.guidance_step_'s arguments after ``dt``."""
         x0 = latents.clone()
-        ops.guidance_step_(noise_pred, x0, t, *guidance, cond_mask=cond_mask, t=t)
+        step_ = ops.guidance_step_ if latents.shape[0] == 1 else ops.guidance_step_batched_
+        step_(noise_pred, x0, t, *guidance, cond_mask=cond_mask, t=t)
         t_next = t - dt
         renoised = (1 - t_next) * x0 + t_next * torch.randn_like(latents)
         if cond_mask is None:
@@ -475,7 +491,15 @@ class LTXVideoPipeline:
 
         Explicit refusals (outside this path): a string ``prompt`` (the reference's ``__call__`` does not encode it
         either: it reads ``prompt_embeds``, :1029-1051 -- ``LTXMultiScalePipeline`` / ``encode_prompt`` do), ``is_video=False``,
-        ``offload_to_cpu``, ``enhance_prompt``, more than one prompt / image per prompt.
+        ``offload_to_cpu``, ``enhance_prompt``.
+
+        Several videos per call: b = ``prompt_embeds.shape[0] * num_images_per_prompt`` (the four prompt tensors are repeated
+        per image here, prompt-major, as ``encode_prompt`` does for text).  The rows into the transformer are the
+        reference's chunks [negative x b, positive x b, perturbed x b]; every sum of the guidance is per video
+        (``ops.guidance_step_batched_``), so video j is what the single call with its inputs gives.  ``generator`` may be a
+        list of b generators (diffusers' ``randn_tensor`` semantics); ``media_items`` and a conditioning item's clip hold b
+        videos or one shared by all; all videos have one token geometry.  ``callback`` gets video 0's preview.  With sequence
+        parallelism installed on the transformer b > 1 is refused.
 
         ``mixed_precision=True`` (:1061, :1152-1156, :1177): the latents are fp32 whatever ``prompt_embeds``' dtype is, and the
         transformer runs with ``mixed=True`` -- an fp32 residual stream between bf16 linears and attention, a bf16
@@ -492,8 +516,18 @@ class LTXVideoPipeline:
         image_cond_noise_scale = kwargs.get("image_cond_noise_scale", 0.0)
         self.check_inputs(prompt, height, width, negative_prompt, prompt_embeds, negative_prompt_embeds,
                           prompt_attention_mask, negative_prompt_attention_mask, enhance_prompt)
-        self._refuse_outside_this_path(prompt, prompt_embeds, is_video, offload_to_cpu,
-                                       num_images_per_prompt * (0 if prompt_embeds is None else prompt_embeds.shape[0]))
+        self._refuse_outside_this_path(prompt, prompt_embeds, is_video, offload_to_cpu)
+        num_images = 1 if num_images_per_prompt is None else int(num_images_per_prompt)
+        if num_images < 1:
+            raise ValueError(f"ltxmi.LTXVideoPipeline: num_images_per_prompt={num_images_per_prompt} must be at least 1")
+        if num_images > 1:
+            # extension: the reference's __call__ sizes the latents by num_images_per_prompt and never repeats the prompt
+            # (:905-925), which only works for one image; repeated here as encode_prompt repeats text (prompt-major)
+            prompt_embeds, prompt_attention_mask = self._per_image(prompt_embeds, prompt_attention_mask, num_images)
+            if negative_prompt_embeds is not None:
+                negative_prompt_embeds, negative_prompt_attention_mask = self._per_image(
+                    negative_prompt_embeds, negative_prompt_attention_mask, num_images)
+        b = prompt_embeds.shape[0]                                                       # videos in this call
         if mixed_precision:
             # :1061: fp32 latents whatever the prompt's dtype; the transformer then keeps its residual stream in fp32 (:1177)
             if latents_dtype not in (None, torch.float32):
@@ -502,10 +536,14 @@ class LTXVideoPipeline:
             latents_dtype = torch.float32
         tr, device = self.transformer, self._execution_device
         holder = self if ltxv_model is None else ltxv_model                              # of ``_interrupt``
+        if b > 1 and getattr(tr, "_sp_interrupt", None) is not None:
+            raise NotImplementedError(f"ltxmi.LTXVideoPipeline: {b} videos in one call (prompts x num_images_per_prompt) on a "
+                                      "transformer with sequence parallelism installed (_sp_interrupt is set): the "
+                                      "multi-GPU paths take one video per call")
 
         grid = (num_frames // self.video_scale_factor + 1, height // self.vae_scale_factor,
                 width // self.vae_scale_factor)                                          # latent f, h, w  :921-923
-        latent_shape = (1, tr.config.in_channels, *grid)
+        latent_shape = (b, tr.config.in_channels, *grid)
         assert strength == 1.0 or latents is not None or media_items is not None, \
             "ltxmi.LTXVideoPipeline: strength < 1 re-noises given content: pass latents or media_items with it"
         timesteps, num_inference_steps = self.retrieve_timesteps(                       # :943-952
@@ -517,7 +555,7 @@ class LTXVideoPipeline:
             assert not outside, f"ltxmi.LTXVideoPipeline: timesteps {outside} are not among {self.allowed_inference_steps}"
         plan = _StepPlan(tr, timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list, guidance_timesteps,
                          (prompt_embeds, prompt_attention_mask), (negative_prompt_embeds, negative_prompt_attention_mask),
-                         device, dead_row_elimination, stg_row_dedup and joint_pass)
+                         device, dead_row_elimination, stg_row_dedup and joint_pass, videos=b)
 
         start = self._initial_latents(latents, media_items, timesteps[0], latent_shape,
                                       prompt_embeds.dtype if latents_dtype is None else latents_dtype,    # :1062
@@ -531,7 +569,8 @@ class LTXVideoPipeline:
         if cond_mask is not None:
             init_latents, cond_mask = latents.clone(), cond_mask.contiguous()
             one_minus_mask = 1.0 - cond_mask
-        frac = pixel_coords.to(torch.float32)
+        # every video of a call has the same token geometry: one table (video 0's) serves all rows
+        frac = pixel_coords[:1].to(torch.float32)
         frac[:, 0] = frac[:, 0] * (1.0 / frame_rate)                                     # :1086-1087
         freqs_cis = tr.precompute_freqs_cis(frac)
 
@@ -540,26 +579,29 @@ class LTXVideoPipeline:
         if callback is not None:                                                         # :1100-1101
             callback(-1, None, True, override_num_inference_steps=num_inference_steps, pass_no=pass_no)
 
-        workspace = torch.empty(ops.GUIDANCE_WORKSPACE_FLOATS, dtype=torch.float32, device=device)
+        workspace = torch.empty(b * ops.GUIDANCE_WORKSPACE_FLOATS, dtype=torch.float32, device=device)
+        guidance_step_ = ops.guidance_step_ if b == 1 else ops.guidance_step_batched_
+        alias_rows = {} if b == 1 else {"stg_alias_rows": b}                             # b = 1: the call as it always was
         t_dev = torch.tensor(timesteps, dtype=torch.float32, device=device)
         for i, t in enumerate(timesteps):
             if cond_mask is not None and image_cond_noise_scale > 0.0:                   # :1105-1113
-                noise = torch.randn(latents.shape, generator=generator, device=device, dtype=latents.dtype)
+                noise = _randn(latents.shape, generator, device, latents.dtype)
                 ops.image_cond_noise_(latents, init_latents, noise, cond_mask, image_cond_noise_scale, t)
             use_cfg, use_stg = plan.rows(i)
-            embeds, mask, nconds = plan.batch(use_cfg, use_stg)
+            embeds, mask, nconds = plan.batch(use_cfg, use_stg)                          # nconds chunks of b rows each
             model_in = latents.to(tr.dtype)
             if nconds > 1:
-                model_in = model_in.expand(nconds, -1, -1)
-            current_timestep = t_dev[i].expand(nconds).unsqueeze(-1)                     # [B_eff, 1]
+                model_in = model_in.expand(nconds, -1, -1) if b == 1 else model_in.repeat(nconds, 1, 1)
+            current_timestep = t_dev[i].expand(nconds * b).unsqueeze(-1)                 # [B_eff, 1]
             if cond_mask is not None:                                                    # :1145-1150, [B_eff, N]
-                current_timestep = torch.minimum(current_timestep, one_minus_mask.expand(nconds, -1))
+                per_row = one_minus_mask.expand(nconds, -1) if b == 1 else one_minus_mask.repeat(nconds, 1)
+                current_timestep = torch.minimum(current_timestep, per_row)
             noise_pred = tr(model_in, freqs_cis=freqs_cis, encoder_hidden_states=embeds,
                             encoder_attention_mask=mask, timestep=current_timestep,
                             stg_alias_blocks=plan.stg_alias_blocks(i, use_stg),
                             skip_layer_mask=plan.skip_mask(i, use_stg, nconds),
                             skip_layer_strategy=skip_layer_strategy, latent_shape=grid, joint_pass=joint_pass,
-                            ltxv_model=holder, mixed=mixed_precision, return_dict=False)[0]
+                            ltxv_model=holder, mixed=mixed_precision, return_dict=False, **alias_rows)[0]
             if noise_pred is None:                                                       # :1180-1181
                 return None
             dt = self.scheduler.host_dt(t)
@@ -567,9 +609,9 @@ class LTXVideoPipeline:
             if stochastic_sampling:
                 self._stochastic_step_(noise_pred, latents, t, dt, guidance, cond_mask, one_minus_mask)
             else:
-                ops.guidance_step_(noise_pred, latents, dt, *guidance, cond_mask=cond_mask, t=t)   # :1183-1241, 1309-1342
-            if callback is not None:                                                     # :1243-1247
-                preview = latents[:, num_cond_latents:].squeeze(0).transpose(0, 1)
+                guidance_step_(noise_pred, latents, dt, *guidance, cond_mask=cond_mask, t=t)   # :1183-1241, 1309-1342
+            if callback is not None:                                                     # :1243-1247: video 0's preview
+                preview = latents[0, num_cond_latents:].transpose(0, 1)
                 callback(i, preview.reshape(preview.shape[0], *grid), False, pass_no=pass_no)
             if callback_on_step_end is not None:
                 callback_on_step_end(self, i, t, {})
@@ -584,7 +626,7 @@ class _StepPlan:
     tables.  The row batches and the skip-layer masks are built when a step first needs them and then kept."""
 
     def __init__(self, transformer, timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list,
-                 guidance_timesteps, positive, negative, device, dead_row_elimination, stg_row_dedup):
+                 guidance_timesteps, positive, negative, device, dead_row_elimination, stg_row_dedup, videos=1):
         self.gs, self.stg, self.rs, self.skip = LTXVideoPipeline._guidance_tables(        # :959-1013
             timesteps, guidance_scale, stg_scale, rescaling_scale, skip_block_list, guidance_timesteps)
         self.do_cfg = any(x > 1.0 for x in self.gs)
@@ -593,6 +635,7 @@ class _StepPlan:
         self.transformer, self.device = transformer, device
         self.positive, self.negative = positive, negative
         self.dead_row_elimination, self.stg_row_dedup = dead_row_elimination, stg_row_dedup
+        self.videos = videos                                     # b: every chunk of the row batch holds b rows
         self._batches, self._skip_masks = {}, {}
 
     def rows(self, i):
@@ -605,7 +648,8 @@ class _StepPlan:
         return (self.do_cfg and self.gs[i] > 1.0), (self.do_stg and self.stg[i] > 0.0)
 
     def batch(self, use_cfg, use_stg):
-        """(embeds, mask, number of rows) in the order negative, positive, STG (= positive again)  :1035-1051."""
+        """(embeds, mask, number of chunks) in the reference's chunk order (:1035-1051): the b negative rows, the b positive
+        rows, the b STG rows (= the positive ones again); the prompt tensors hold one row per video."""
         key = (use_cfg, use_stg)
         if key not in self._batches:
             (e, m), (negative_e, negative_m) = self.positive, self.negative
@@ -616,15 +660,30 @@ class _StepPlan:
             if use_stg:
                 e = torch.cat([e, self.positive[0]], dim=0)
                 m = torch.cat([m, self.positive[1].to(self.device)], dim=0)
-            self._batches[key] = (e.to(device=self.device, dtype=self.transformer.dtype), m, e.shape[0])
+            self._batches[key] = (e.to(device=self.device, dtype=self.transformer.dtype), m, e.shape[0] // self.videos)
         return self._batches[key]
 
     def skip_mask(self, i, use_stg, nconds):                                             # :1016-1026
+        """[layers, nconds * b]: zero for the perturbed rows at the step's skipped blocks, one elsewhere.  The reference's
+        ``create_skip_layer_mask`` zeroes rows ``ptb_index::num_conds`` (an interleaved batch) while the batch it is applied
+        to is chunked (:1035-1051, :1184-1188); the two agree for one video only.  For b videos the perturbed chunk is the
+        LAST b rows, and that is what is zeroed here (``create_skip_layer_mask`` itself stays the reference's)."""
         if not use_stg or self.skip is None:
             return None
         key = (tuple(self.skip[i]), nconds)
         if key not in self._skip_masks:
-            self._skip_masks[key] = self.transformer.create_skip_layer_mask(1, nconds, nconds - 1, list(self.skip[i]))
+            tr, b = self.transformer, self.videos
+            if b == 1:
+                self._skip_masks[key] = tr.create_skip_layer_mask(1, nconds, nconds - 1, list(self.skip[i]))
+            elif len(self.skip[i]) == 0:
+                self._skip_masks[key] = None
+            else:
+                host = torch.ones((len(tr.transformer_blocks), nconds * b), dtype=torch.float32)
+                for block in self.skip[i]:
+                    host[block, (nconds - 1) * b:] = 0
+                mask = host.to(device=tr.device, dtype=tr.dtype)
+                mask._ltxmi_host_rows = [[float(x) for x in row] for row in host.tolist()]   # no D2H copy per forward
+                self._skip_masks[key] = mask
         return self._skip_masks[key]
 
     def stg_alias_blocks(self, i, use_stg):
@@ -675,8 +734,11 @@ class LTXMultiScalePipeline:
         shared = {k: v for k, v in kwargs.items() if k not in ("prompt", "negative_prompt")}
         if kwargs.get("prompt") is not None or shared.get("prompt_embeds") is None:     # :1833-1852
             names = ("prompt_embeds", "prompt_attention_mask", "negative_prompt_embeds", "negative_prompt_attention_mask")
+            # a list of prompts and num_images_per_prompt give prompts x images rows here; the passes must not repeat them again
             shared.update(zip(names, vp.encode_prompt(kwargs.get("prompt"), True, negative_prompt=kwargs.get("negative_prompt"),
+                                                      num_images_per_prompt=shared.get("num_images_per_prompt") or 1,
                                                       device=shared.get("device"), text_encoder_max_tokens=256)))
+            shared["num_images_per_prompt"] = 1
         if getattr(shared.get("ltxv_model"), "_interrupt", False):
             return None
 

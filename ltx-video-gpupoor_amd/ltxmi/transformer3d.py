@@ -273,7 +273,7 @@ class Transformer3DModel(nn.Module):
                 skip_layer_mask: Optional[torch.Tensor] = None,
                 skip_layer_strategy: Optional[SkipLayerStrategy] = None, latent_shape=None, joint_pass=True,
                 ltxv_model=None, mixed=False, return_dict: bool = True, stg_alias_blocks: int = 0,
-                _microbatches=None):
+                stg_alias_rows: int = 1, _microbatches=None):
         """``stg_alias_blocks`` (extension, default off): the caller guarantees that the LAST batch row has
         exactly the inputs of the row before it (the STG "perturbed" row is the text row until its first
         skipped block, pipeline_ltx_video.py:1035-1051) -- the first ``stg_alias_blocks`` blocks then run on
@@ -281,6 +281,9 @@ class Transformer3DModel(nn.Module):
         computes a row independently of the others, the GEMM kernels all accumulate over K in the same order and share
         their epilogue arithmetic (so the tile choice made from M does not matter), and the request is ignored when
         B - 1 and B rows would be served by different self-attention kernels (``ops.attention_kernel_id``).
+        ``stg_alias_rows`` = r (default 1: the above): with r videos in the call the batch is chunked (uncond x r, text x r,
+        perturbed x r), so the last r rows have the inputs of the r rows before them; the leading blocks run on B - r rows
+        and the last r rows are filled by one copy.
         ``_microbatches`` (extension, set by ltxmi.distributed): a list of batch-row slices; the block loop then runs
         every block once per slice, each slice on a stream of its own, so that one slice's collectives (sequence
         parallelism) are hidden behind the other slices' kernels.  Rows are independent: same result.
@@ -355,13 +358,16 @@ class Transformer3DModel(nn.Module):
             return m
 
         first_block = 0
-        if joint_pass and stg_alias_blocks and B >= 2:
+        r = int(stg_alias_rows)
+        if stg_alias_blocks and r < 1:
+            raise ValueError(f"ltxmi.Transformer3DModel: stg_alias_rows={stg_alias_rows} must be at least 1")
+        if joint_pass and stg_alias_blocks and B >= 2 * r:
             heads, dh = self.num_attention_heads, self.attention_head_dim
-            if ops.attention_kernel_id(B, heads, N, N, dh) != ops.attention_kernel_id(B - 1, heads, N, N, dh):
+            if ops.attention_kernel_id(B, heads, N, N, dh) != ops.attention_kernel_id(B - r, heads, N, N, dh):
                 stg_alias_blocks = 0                                        # a sub-batch would not reproduce the full batch's bits
-        if joint_pass and stg_alias_blocks and B >= 2:
+        if joint_pass and stg_alias_blocks and B >= 2 * r:
             first_block = min(int(stg_alias_blocks), len(self.transformer_blocks))
-            keep = slice(0, B - 1)
+            keep = slice(0, B - r)
             hs = hidden_states[keep]                                        # a view: the blocks update it in place
             for block_idx in range(first_block):
                 self.transformer_blocks[block_idx](
@@ -372,7 +378,7 @@ class Transformer3DModel(nn.Module):
                     skip_layer_mask=layer_mask(block_idx, keep), skip_layer_strategy=skip_layer_strategy)
                 if ltxv_model is not None and ltxv_model._interrupt:
                     return [None]
-            hidden_states[B - 1].copy_(hidden_states[B - 2])
+            hidden_states[B - r:].copy_(hidden_states[B - 2 * r:B - r])
         if joint_pass and _microbatches and len(_microbatches) > 1 and first_block == 0:
             if self._run_blocks_microbatched(hidden_states, _microbatches, freqs_cis, attention_mask, encoder_hidden_states,
                                              encoder_attention_mask, temb, cross_attention_kwargs, class_labels,
