@@ -23,7 +23,8 @@
  *     of ltxmi_attn_args; 0.3: q_rstd*; 0.4: conv3d post_*; 0.5: redo_counter, force_exact of ltxmi_attn_args, y_norm, workspace of ltxmi_conv3d_args;
  *     0.6: lse* of ltxmi_attn_args; 0.7: no field -- ltxmi_gemm_kernel_id, ltxmi_conv3d_route, ltxmi_gemm_args.algo = 256 is honoured for every
  *     shape, and the GEMM entry check refuses a bad epilogue and a residual / gate pointer off an 8-byte boundary;
- *     0.8: no field -- ltxmi_norm_modulate_f32in_bf16 and ltxmi_gate_residual_f32, the row passes of the fp32 residual stream),
+ *     0.8: no field -- ltxmi_norm_modulate_f32in_bf16 and ltxmi_gate_residual_f32, the row passes of the fp32 residual stream;
+ *     0.9: no field -- pad_replicate = 2, and ltxmi_gemm_pair2_bf16 / ltxmi_gemm_pair2_kernel_id with a struct of their own),
  *     and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
  *     switches its companion size / stride fields off whatever they hold.
@@ -116,6 +117,40 @@ int ltxmi_gemm_bf16(const ltxmi_gemm_args* args, void* stream);
  * algo = 128 / 256 give id 0 / 1 for every accepted shape.  Every kernel accumulates over K in the same order: for the same
  * arguments the three produce the same bits. */
 int ltxmi_gemm_kernel_id(const ltxmi_gemm_args* args);
+
+/* ---------------------------------------------------------------------------------
+ * GEMM with a second operand pair (0.9): LoRA adapters applied unmerged
+ *   C[M,N] = epilogue(A[M,K] . W[N,K]^T + A2[M, g*K2 .. (g+1)*K2) . W2[N,K2]^T + bias[N]),   g = n / group_cols
+ *
+ * Replaces what the reference does to run a LoRA file on top of unchanged base weights: inference.py:483-493 hands the
+ * adapter files to offload.load_loras_into_model(..., activate_all_loras=True), which patches every nn.Linear the file
+ * names so that it computes base(x) + s * up(down(x)); ltxv.py:160-161 keeps the LoRA file apart from the model files.
+ * Here A2 = bf16(x . down^T) (one ltxmi_gemm_bf16 call) and W2 = bf16(s * up): the second pair continues the K loop of the
+ * first, so the epilogues (GELU, gate + residual, the row sums of squares) see the adapter inside the accumulator, and
+ * (A, W) stay exactly what ltxmi_gemm_bf16 takes -- the adapter rank enters no pitch of the caller's.  A packed
+ * projection (q, k, v stacked along N) takes a packed adapter: `group_cols` output columns per member, member g reading
+ * columns [g*K2, (g+1)*K2) of A2.
+ * The K-tiles of (A, W), then those of (A2, W2), are accumulated in order, as every kernel of ltxmi_gemm_bf16 does for
+ * one K: a call equals ltxmi_gemm_bf16 on the concatenation [A | A2_g], [W | W2] with K = K + K2, bit for bit.
+ * `args` is checked as ltxmi_gemm_bf16 checks it (every field keeps its meaning; algo 128 / 256 force a tile form), then:
+ * LTXMI_ERR_INVALID_ARG for a NULL pair, A2 or W2, a K2 that is not a positive multiple of 64, a group_cols that is
+ * neither 0 nor a multiple of 128 that divides N, algo = 256 with a group_cols that is not a multiple of 256;
+ * LTXMI_ERR_UNSUPPORTED for a_kblock != 0, A2 or W2 off a 16-byte boundary, lda2 or ldw2 % 8 != 0, lda2 < groups * K2,
+ * ldw2 < K2, or an operand whose 256-row panel spans 2 GiB.
+ * ------------------------------------------------------------------------------- */
+typedef struct ltxmi_gemm_pair {
+    const void* A2; int64_t lda2;     /* [M, groups*K2] bf16, 16-byte aligned, lda2 % 8 == 0            */
+    const void* W2; int64_t ldw2;     /* [N, K2] bf16, 16-byte aligned, ldw2 % 8 == 0, ldw2 >= K2       */
+    int32_t K2;                       /* > 0, multiple of 64                                            */
+    int32_t group_cols;               /* 0 = one group; else N % group_cols == 0, group_cols % 128 == 0 */
+} ltxmi_gemm_pair;
+
+int ltxmi_gemm_pair2_bf16(const ltxmi_gemm_args* args, const ltxmi_gemm_pair* pair, void* stream);
+/* Which kernel ltxmi_gemm_pair2_bf16 runs: 3 = the 128x128 two-pair kernel, 4 = the 256x256 one, or the negative
+ * ltxmi_status the launch would return.  Host arithmetic only, as ltxmi_gemm_kernel_id.  By shape (algo = 0): 4 when
+ * M >= 768, N >= 256, ceil(M/256) * ceil(N/256) >= 128 and group_cols % 256 == 0 (0 included); else 3.  The two produce
+ * the same bits. */
+int ltxmi_gemm_pair2_kernel_id(const ltxmi_gemm_args* args, const ltxmi_gemm_pair* pair);
 
 /* ---------------------------------------------------------------------------------
  * Fused standardisation + AdaLN modulation

@@ -19,6 +19,23 @@ template <class V>
 __device__ __forceinline__ u32x2 pack_bf16x4(V&& v) {
     return u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
 }
+// ---- the dense GEMMs' internal epilogues, beside the public ltxmi_epilogue values (gemm.hip, gemm_pair2.hip)
+constexpr int EPI_RESIDUAL = 5;   // internal: GATE_RESIDUAL without a gate (C = R + acc + bias)
+constexpr int EPI_SUMSQ = 6;      // internal: plain store + per-(row, 64-column block) sum of squares of the stored bf16
+                                  // values for the columns < sumsq_cols (the q part of a fused QKV projection: the
+                                  // attention kernel turns them into q's RMSNorm factor, attention.py:1040-1041)
+
+// s + the squares of four stored bf16 values, as ONE fixed chain of fused multiply-adds: under -ffast-math hipcc is free to
+// associate "s += a*a + b*b + c*c + d*d" differently in every kernel instance, and the row sums of squares (which become
+// q's RMSNorm factor) must not depend on which GEMM kernel the dispatcher picked for a given M
+__device__ __forceinline__ float sumsq4(float s, u32x2 o) {
+    s = __builtin_fmaf(bf_lo(o[0]), bf_lo(o[0]), s);
+    s = __builtin_fmaf(bf_hi(o[0]), bf_hi(o[0]), s);
+    s = __builtin_fmaf(bf_lo(o[1]), bf_lo(o[1]), s);
+    s = __builtin_fmaf(bf_hi(o[1]), bf_hi(o[1]), s);
+    return s;
+}
+
 // ---- a wave's 4-KB LDS scratch: 32 rows x 128 B (64 bf16 columns), 16-byte chunks XOR-swizzled by row & 7; written in the
 // accumulators' layout and read row-major, or the other way round.  Both return the ADDRESS, formed term by term: hipcc folds the
 // row term's constant part into the instruction's offset field only then.  The 8-byte piece of fragment column j in row row_l:

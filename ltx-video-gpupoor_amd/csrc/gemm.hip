@@ -64,26 +64,12 @@ struct GemmParams {
 };
 
 constexpr int EPI_D2S = 4;   // internal: conv + pixel-shuffle(2,2,2) scatter (+ residual)
-constexpr int EPI_RESIDUAL = 5;   // internal: GATE_RESIDUAL without a gate (C = R + acc + bias)
-constexpr int EPI_SUMSQ = 6;      // internal: plain store + per-(row, 64-column block) sum of squares of the stored bf16
-                                  // values for the columns < sumsq_cols (the q part of a fused QKV projection: the
-                                  // attention kernel turns them into q's RMSNorm factor, attention.py:1040-1041)
+// (EPI_RESIDUAL, EPI_SUMSQ and sumsq4: epilogue.h, shared with gemm_pair2.hip)
 
 // 64 zero bytes: LDS-DMA source for zero-padded taps
 __device__ __attribute__((aligned(16))) uint32_t g_zero_page[16];
 
 constexpr int BK = 64;
-
-// s + the squares of four stored bf16 values, as ONE fixed chain of fused multiply-adds: under -ffast-math hipcc is free to
-// associate "s += a*a + b*b + c*c + d*d" differently in every kernel instance, and the row sums of squares (which become
-// q's RMSNorm factor) must not depend on which GEMM kernel the dispatcher picked for a given M
-__device__ __forceinline__ float sumsq4(float s, u32x2 o) {
-    s = __builtin_fmaf(bf_lo(o[0]), bf_lo(o[0]), s);
-    s = __builtin_fmaf(bf_hi(o[0]), bf_hi(o[0]), s);
-    s = __builtin_fmaf(bf_lo(o[1]), bf_lo(o[1]), s);
-    s = __builtin_fmaf(bf_hi(o[1]), bf_hi(o[1]), s);
-    return s;
-}
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int MODE>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(GemmParams p) {

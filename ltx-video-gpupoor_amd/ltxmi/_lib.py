@@ -28,6 +28,10 @@ class GemmArgs(ctypes.Structure):
                 ("a_kblock", c_int), ("a_kblock_stride", c_int64)]
 
 
+class GemmPair(ctypes.Structure):
+    _fields_ = [("A2", c_void_p), ("lda2", c_int64), ("W2", c_void_p), ("ldw2", c_int64), ("K2", c_int), ("group_cols", c_int)]
+
+
 class AttnArgs(ctypes.Structure):
     _fields_ = [("q", c_void_p), ("q_stride_b", c_int64), ("q_stride_l", c_int64),
                 ("k", c_void_p), ("k_stride_b", c_int64), ("k_stride_l", c_int64),
@@ -81,6 +85,8 @@ SIGNATURES = {
     "ltxmi_arch": (ctypes.c_char_p, []),
     "ltxmi_gemm_bf16": (c_int, [ctypes.POINTER(GemmArgs), c_void_p]),
     "ltxmi_gemm_kernel_id": (c_int, [ctypes.POINTER(GemmArgs)]),
+    "ltxmi_gemm_pair2_bf16": (c_int, [ctypes.POINTER(GemmArgs), ctypes.POINTER(GemmPair), c_void_p]),
+    "ltxmi_gemm_pair2_kernel_id": (c_int, [ctypes.POINTER(GemmArgs), ctypes.POINTER(GemmPair)]),
     "ltxmi_norm_modulate_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "ltxmi_norm_modulate_f32in_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_int,

@@ -26,7 +26,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from . import ops
+from . import lora, ops
 from .attention_seam import pay_attention
 
 BF16 = torch.bfloat16
@@ -97,8 +97,9 @@ class FeedForward(nn.Module):
                                   nn.Linear(inner_dim, dim_out, bias=bias)])
 
     def forward(self, hidden_states, scale: float = 1.0):
-        h = ops.gemm(hidden_states, self.net[0].proj.weight, self.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH)
-        out = ops.gemm(h, self.net[2].weight, self.net[2].bias)
+        h = ops.gemm(hidden_states, self.net[0].proj.weight, self.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH,
+                     **lora.pair(self, "ff1", hidden_states))
+        out = ops.gemm(h, self.net[2].weight, self.net[2].bias, **lora.pair(self, "ff2", h))
         return out.view(*hidden_states.shape[:-1], out.shape[-1])
 
 
@@ -255,7 +256,8 @@ class AttnProcessor2_0:
             # its own: the only launch between the projection and attention is k's norm + RoPE.
             fuse_q = ops.attention_fuses_qnorm(B, H, N, N, dh) and D % 64 == 0 and attention_mask is None
             ss = torch.empty((B * N, D // 64), dtype=torch.float32, device=x2.device) if fuse_q else None
-            qkv = ops.gemm(x2, wqkv, bqkv, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0)   # [B*N, 3D]
+            qkv = ops.gemm(x2, wqkv, bqkv, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0,
+                           **lora.pair(attn, "qkv", x2))                                    # [B*N, 3D]
             q2, k2, v2 = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
             cos = sin = None
             period = 0
@@ -290,14 +292,17 @@ class AttnProcessor2_0:
             # step, tools/bench_xattn_fuse.py).
             fuse_q = FUSE_CROSS_ATTENTION_Q and D % 64 == 0 and bool(ops.attention_fuses_qnorm(B, H, N, Lk, dh, attention_mask is not None))
             ss = torch.empty((B * N, D // 64), dtype=torch.float32, device=x2.device) if fuse_q else None
-            q2 = ops.gemm(x2, attn.to_q.weight, attn.to_q.bias, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0)   # [B*N, D]
+            q2 = ops.gemm(x2, attn.to_q.weight, attn.to_q.bias, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0,
+                          **lora.pair(attn, "q", x2))                                      # [B*N, D]
             # The text keys/values depend on the prompt and this layer's weights only: within a generation
             # they are the same at every denoise step, so they are projected + normalised once and reused
             # (same kernels on the same inputs: identical values).  Keyed on storage + version of the inputs;
-            # the source tensors are kept alive so an address cannot be reused while the entry exists.
+            # the source tensors are kept alive so an address cannot be reused while the entry exists.  An adapter on
+            # to_k / to_v changes the projection without touching a weight: the adapter epoch (bumped by attach / detach /
+            # set_lora_weights) is part of the key.
             ehs = encoder_hidden_states
             key = (ehs.data_ptr(), tuple(ehs.shape), ops.tensor_version(ehs), wkv.data_ptr(), ops.tensor_version(wkv),
-                   attn.k_norm.weight.data_ptr(), ops.tensor_version(attn.k_norm.weight))
+                   attn.k_norm.weight.data_ptr(), ops.tensor_version(attn.k_norm.weight), lora.epoch(attn))
             cache = attn.__dict__.setdefault("_text_kv_cache", {})
             hit = cache.get(key) if ops.STEP_INVARIANT_CACHING else None
             if hit is None:
@@ -307,16 +312,17 @@ class AttnProcessor2_0:
                 # full tensor is served; the entry lives until the end of the forward (Transformer3DModel.forward drops it)
                 ready = attn.__dict__.get("_text_kv_ready")
                 if ready is not None:
-                    full, full_version, kv_full = ready
+                    full, full_version, kv_full, ready_epoch = ready
                     row_bytes = full.stride(0) * full.element_size()
                     off = ehs.data_ptr() - full.data_ptr()
                     if (row_bytes > 0 and off >= 0 and off % row_bytes == 0 and ehs.shape[1:] == full.shape[1:]
                             and off // row_bytes + Bk <= full.shape[0] and ehs.dtype == full.dtype and ehs.is_contiguous()
-                            and ops.tensor_version(full) == full_version):
+                            and ops.tensor_version(full) == full_version and ready_epoch == lora.epoch(attn)):
                         r0 = off // row_bytes
                         hit = (kv_full[r0 * Lk:(r0 + Bk) * Lk],)
             if hit is None:
-                kv = ops.gemm(ehs.reshape(Bk * Lk, -1), wkv, bkv)                  # [B*Lk, 2D]
+                e2 = ehs.reshape(Bk * Lk, -1)
+                kv = ops.gemm(e2, wkv, bkv, **lora.pair(attn, "kv", e2))           # [B*Lk, 2D]
                 ops.rmsnorm_rope_(kv[:, :D], attn.k_norm.weight, attn.k_norm.eps)
                 if len(cache) >= 4:
                     cache.clear()
@@ -362,9 +368,10 @@ class AttnProcessor2_0:
             residual, gate_table, gate_temb, rpg = fused_residual
             ops.gemm(a3.reshape(B * N, D), w_o, b_o, out=residual.reshape(B * N, -1),
                      epilogue=ops.EPI_GATE_RESIDUAL, residual=residual.reshape(B * N, -1),
-                     gate_table=gate_table, gate_temb=gate_temb, rows_per_group=rpg)
+                     gate_table=gate_table, gate_temb=gate_temb, rows_per_group=rpg,
+                     **lora.pair(attn, "out", a3.reshape(B * N, D)))
             return residual
-        out = ops.gemm(a3.reshape(B * N, D), w_o, b_o).view(B, N, -1)
+        out = ops.gemm(a3.reshape(B * N, D), w_o, b_o, **lora.pair(attn, "out", a3.reshape(B * N, D))).view(B, N, -1)
         if attn.residual_connection or attn.rescale_output_factor != 1.0:
             raise NotImplementedError("ltxmi.AttnProcessor2_0: residual_connection / rescale_output_factor")
         return out
@@ -466,11 +473,11 @@ class BasicTransformerBlock(nn.Module):
         sh_t, sh_e = chunk(3)
         ops.norm_modulate(h2, norm_h.view(B * N, D), self.norm2.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
         ff1 = ops.gemm(norm_h.view(B * N, D), self.ff.net[0].proj.weight, self.ff.net[0].proj.bias,
-                       epilogue=ops.EPI_GELU_TANH)
+                       epilogue=ops.EPI_GELU_TANH, **lora.pair(self.ff, "ff1", norm_h.view(B * N, D)))
         del norm_h
         g_t, g_e = chunk(5)
         ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=h2, epilogue=ops.EPI_GATE_RESIDUAL,
-                 residual=h2, gate_table=g_t, gate_temb=g_e, rows_per_group=rpg)
+                 residual=h2, gate_table=g_t, gate_temb=g_e, rows_per_group=rpg, **lora.pair(self.ff, "ff2", ff1))
         del ff1
 
         if block_skip:
@@ -517,8 +524,9 @@ class BasicTransformerBlock(nn.Module):
         sc_t, sc_e = chunk(4)
         sh_t, sh_e = chunk(3)
         ops.norm_modulate_f32in(h2, norm_h, self.norm2.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
-        ff1 = ops.gemm(norm_h, self.ff.net[0].proj.weight, self.ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH)
-        ff2 = ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=norm_h)
+        ff1 = ops.gemm(norm_h, self.ff.net[0].proj.weight, self.ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH,
+                       **lora.pair(self.ff, "ff1", norm_h))
+        ff2 = ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=norm_h, **lora.pair(self.ff, "ff2", ff1))
         del ff1
         g_t, g_e = chunk(5)
         ops.gate_residual_f32_(h2, ff2, g_t, g_e, rpg, round_product=0)

@@ -194,6 +194,12 @@ def _refuse_fp32_stream(who):
                               "built for sequence parallelism; run it on one GPU or use the bf16 stream")
 
 
+def _refuse_lora(owner, who):
+    """Adapters (ltxmi/lora.py) are not carried through the exchanges: ``owner`` (an Attention, or the model) must hold none."""
+    from . import lora
+    lora.refuse(owner, f"ltxmi.distributed.{who}")
+
+
 class UlyssesAttnProcessor:
     """Replaces AttnProcessor2_0 on ``attn1`` of every block (installed with ``Attention.set_processor``): identical
     math, plus the two all-to-alls -- which run directly on the buffers the kernels write and read:
@@ -245,6 +251,7 @@ class UlyssesAttnProcessor:
         hidden_states = hidden_states_wrapper[0]
         hidden_states_wrapper.clear()
         assert encoder_hidden_states is None, "UlyssesAttnProcessor is for self-attention"
+        _refuse_lora(attn, "UlyssesAttnProcessor")
         if attention_mask is not None:
             raise NotImplementedError("UlyssesAttnProcessor: a self-attention mask is not on this path")
         P = self.simulate_world or dist.get_world_size(self.group)
@@ -312,6 +319,10 @@ class RingAttnProcessor(AttnProcessor2_0):
 
     def refuse_fp32_stream(self):
         _refuse_fp32_stream("RingAttnProcessor")
+
+    def __call__(self, attn, *args, **kwargs):
+        _refuse_lora(attn, "RingAttnProcessor")
+        return super().__call__(attn, *args, **kwargs)
 
     def attend(self, qkv_list, is_cross, **kw):
         if is_cross:
@@ -462,6 +473,7 @@ def usp_dit_forward(model, hidden_states, freqs_cis, encoder_hidden_states=None,
     path -- and here it wraps ``Transformer3DModel.forward`` and so takes THAT method's arguments."""
     if kw.get("mixed"):
         _refuse_fp32_stream("usp_dit_forward")
+    _refuse_lora(model, "usp_dit_forward")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     N = hidden_states.shape[1]
     hs = shard_tokens(hidden_states, rank, world)

@@ -135,6 +135,67 @@ def load_transformer(path, device="cuda", dtype=torch.bfloat16):
     return model.eval()
 
 
+LORA_PREFIXES = ("model.diffusion_model.", "diffusion_model.", "transformer.")
+LORA_DOWN, LORA_UP = (".lora_A.weight", ".lora_down.weight"), (".lora_B.weight", ".lora_up.weight")
+
+
+def load_lora(path_or_state_dict, device="cpu"):
+    """A LoRA file (safetensors) or its state dict -> ``lora.LoraAdapter`` for ``Transformer3DModel.attach_lora``.
+
+    Keys: ``<prefix><module>.lora_A.weight`` or ``.lora_down.weight`` ([r, in]), ``<module>.lora_B.weight`` or ``.lora_up.weight``
+    ([out, r]) and an optional scalar ``<module>.alpha``; the prefixes ``diffusion_model.``, ``model.diffusion_model.``,
+    ``transformer.`` or none are stripped; ``<module>`` is the reference's module path (``transformer_blocks.7.attn1.to_q``,
+    ``...attn2.to_out.0``, ``...ff.net.0.proj``, ``...ff.net.2``).  Raises on a half pair, on shapes that do not make a pair, and
+    on a key that names no linear of the model (that a pair fits ITS linear is checked by ``attach_lora``, which has the model).
+    What the reference does with the file: inference.py:452-455,483-493 (``offload.load_loras_into_model``)."""
+    from . import lora
+    if isinstance(path_or_state_dict, dict):
+        sd = path_or_state_dict
+    else:
+        path = str(path_or_state_dict)
+        if not path.endswith(".safetensors"):
+            raise ValueError(f"ltxmi.load_lora: only safetensors files are read, got {path}")
+        sd, _ = _read_safetensors(path, device)
+    parts = {}
+    for key, t in sd.items():
+        k = key
+        for pre in LORA_PREFIXES:
+            if k.startswith(pre):
+                k = k[len(pre):]
+                break
+        for kind, suffixes in (("down", LORA_DOWN), ("up", LORA_UP), ("alpha", (".alpha",))):
+            hit = [s for s in suffixes if k.endswith(s)]
+            if hit:
+                module = k[:-len(hit[0])]
+                break
+        else:
+            raise KeyError(f"ltxmi.load_lora: '{key}' is neither a lora_A / lora_down, a lora_B / lora_up nor an alpha")
+        known = module in lora.OTHER_LINEARS
+        p = module.split(".", 2)
+        known = known or (len(p) == 3 and p[0] == "transformer_blocks" and p[1].isdigit() and p[2] in lora.BLOCK_TARGETS)
+        if not known:
+            raise KeyError(f"ltxmi.load_lora: '{key}' names no linear of the model ('{module}')")
+        if kind in parts.setdefault(module, {}):
+            raise KeyError(f"ltxmi.load_lora: '{module}' has two {kind} tensors")
+        parts[module][kind] = t
+    modules = {}
+    for module, d in parts.items():
+        if "down" not in d or "up" not in d:
+            raise KeyError(f"ltxmi.load_lora: '{module}' has only half a pair ({', '.join(sorted(d))})")
+        down, up = d["down"], d["up"]
+        if down.dim() != 2 or up.dim() != 2 or up.shape[1] != down.shape[0]:
+            raise ValueError(f"ltxmi.load_lora: '{module}': down {tuple(down.shape)} and up {tuple(up.shape)} do not make a pair")
+        alpha = d.get("alpha")
+        if alpha is not None:
+            if alpha.numel() != 1:
+                raise ValueError(f"ltxmi.load_lora: '{module}.alpha' is not a scalar")
+            alpha = float(alpha.reshape(()).float())
+        modules[module] = (down, up, alpha)
+    if not modules:
+        raise ValueError("ltxmi.load_lora: no adapter tensors found")
+    return lora.LoraAdapter(modules)
+
+
 def load_vae(path, device="cuda", dtype=torch.bfloat16, with_encoder=True):
     """Build ``CausalVideoAutoencoder`` from a checkpoint (``with_encoder=False``: decode side only)."""
     from .autoencoder import CausalVideoAutoencoder

@@ -1,0 +1,176 @@
+"""LoRA adapters on the linears of the DiT blocks, applied UNMERGED at run time on top of unchanged base weights.
+
+The reference's default 13B setup is a dev checkpoint plus a rank-128 "distilled" LoRA file (inference.py:99,408), handed to
+``offload.load_loras_into_model(..., activate_all_loras=True)`` (inference.py:452-455,483-493; ltxv.py:160-161 keeps the file
+apart from the model files): every linear the file names then computes ``base(x) + s * up(down(x))``, ``s = weight * alpha / r``.
+
+Here the same formula is two GEMM launches per linear: ``T = bf16(x . down^T)`` on the existing kernel, then the linear's own
+call with the second operand pair ``a2 = T, w2 = bf16(s * up)`` (``ops.gemm``, ltxmi_gemm_pair2_bf16), so the adapter arrives
+inside the accumulator and every fused epilogue -- GELU, gate + residual, q's row sums of squares -- sees it.  Several adapters
+on one linear are one pair: their down matrices stacked along r, their scaled up matrices side by side.  The packed projections
+take packed adapters: ``down = [down_q; down_k; down_v]``, one ``T [M, 3R]``, ``up = [up_q; up_k; up_v]`` with member g reading
+columns [g R, (g + 1) R) of T (``a2_group_cols = D``); a member without an adapter contributes zero blocks.
+
+State per linear (``LoraSlot``) is rebuilt on attach / detach / weight change, cost O(adapter); with no adapter attached no
+slot exists and every call the package makes is the one it makes without this module."""
+from collections import OrderedDict
+
+import torch
+
+from . import ops
+
+BF16 = torch.bfloat16
+RANK_PAD = 64          # include/ltxmi.h: K2 of ltxmi_gemm_pair is a multiple of 64
+
+# the ten linears of a BasicTransformerBlock, by their path below ``transformer_blocks.<i>.``
+BLOCK_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v",
+                 "attn2.to_out.0", "ff.net.0.proj", "ff.net.2")
+# linears an adapter file may name that carry no adapter here (attach_lora: strict=True raises, strict=False skips them)
+OTHER_LINEARS = ("patchify_proj", "adaln_single.emb.timestep_embedder.linear_1", "adaln_single.emb.timestep_embedder.linear_2",
+                 "adaln_single.linear", "caption_projection.linear_1", "caption_projection.linear_2", "proj_out")
+# (owner module below the block, slot name, member linears below the owner): a slot with several members is a packed projection
+SLOTS = (("attn1", "qkv", ("to_q", "to_k", "to_v")), ("attn1", "out", ("to_out.0",)),
+         ("attn2", "q", ("to_q",)), ("attn2", "kv", ("to_k", "to_v")), ("attn2", "out", ("to_out.0",)),
+         ("ff", "ff1", ("net.0.proj",)), ("ff", "ff2", ("net.2",)))
+
+
+class LoraAdapter:
+    """``modules``: {module path: (down [r, in], up [out, r], alpha or None)} as loaded (``loading.load_lora``)."""
+
+    def __init__(self, modules):
+        self.modules = dict(modules)
+
+    def scale(self, path, weight):
+        down, _, alpha = self.modules[path]
+        return float(weight) * (float(alpha) / down.shape[0] if alpha is not None else 1.0)
+
+
+class LoraSlot:
+    """down [G R, K], up [N, R] (both bf16, R a multiple of 64) and the group width (0: one group) of one GEMM call."""
+    __slots__ = ("down", "up", "group_cols")
+
+    def __init__(self, down, up, group_cols):
+        self.down, self.up, self.group_cols = down, up, group_cols
+
+
+def pair(owner, slot, x2):
+    """Keyword arguments of the second operand pair for ``ops.gemm`` at a call site: {} without an adapter on that linear
+    (the call is then the one it always was), else ``T = ops.gemm(x2, down)`` -- rounded to bf16 once -- and the scaled ups."""
+    slots = owner.__dict__.get("_lora")
+    s = slots.get(slot) if slots else None
+    if s is None:
+        return {}
+    return dict(a2=ops.gemm(x2, s.down), w2=s.up, a2_group_cols=s.group_cols)
+
+
+def has_slot(owner, slot):
+    slots = owner.__dict__.get("_lora")
+    return bool(slots) and slot in slots
+
+
+def epoch(owner):
+    """Bumped on every attach / detach / weight change: part of the key of every cache that holds an adapted projection."""
+    return owner.__dict__.get("_lora_epoch", 0)
+
+
+def refuse(model_or_attn, what):
+    """The sequence-parallel paths carry no adapters: raise, in the style of ``refuse_fp32_stream``."""
+    if model_or_attn.__dict__.get("_lora") or model_or_attn.__dict__.get("_lora_adapters"):
+        raise NotImplementedError(f"ltxmi: {what} does not run LoRA adapters; detach_lora() first or use AttnProcessor2_0")
+
+
+def _get(module, path):
+    for p in path.split("."):
+        module = module[int(p)] if p.isdigit() else getattr(module, p)
+    return module
+
+
+def _member_state(linear, entries):
+    """(down_cat [R, K], up_cat [N, R]) of one linear for ``entries`` = [(down, up, s), ...]; R not yet padded."""
+    w = linear.weight
+    downs = [d.to(device=w.device, dtype=BF16) for d, _, _ in entries]
+    ups = [(u.to(device=w.device, dtype=torch.float32) * s).to(BF16) for _, u, s in entries]
+    return torch.cat(downs, 0), torch.cat(ups, 1)
+
+
+def _pad_to(t, rows=None, cols=None):
+    r, c = t.shape
+    out = torch.zeros((rows or r, cols or c), dtype=t.dtype, device=t.device)
+    out[:r, :c] = t
+    return out
+
+
+def split_targets(adapter, num_blocks):
+    """(block entries {(block, target): path}, other linears named) of an adapter; raises on a path that names no module."""
+    mine, other = {}, []
+    for path in adapter.modules:
+        if path in OTHER_LINEARS:
+            other.append(path)
+            continue
+        parts = path.split(".", 2)
+        if len(parts) == 3 and parts[0] == "transformer_blocks" and parts[1].isdigit() and parts[2] in BLOCK_TARGETS \
+                and int(parts[1]) < num_blocks:
+            mine[(int(parts[1]), parts[2])] = path
+        else:
+            raise KeyError(f"ltxmi.lora: '{path}' names no linear of this model")
+    return mine, sorted(other)
+
+
+def check_shapes(model, adapter, mine):
+    for (i, target), path in mine.items():
+        block = model.transformer_blocks[i]
+        owner = getattr(block, target.split(".")[0], None)
+        if owner is None:
+            raise KeyError(f"ltxmi.lora: '{path}' names no linear of this model")
+        lin = _get(block, target)
+        down, up, _ = adapter.modules[path]
+        if down.shape[1] != lin.weight.shape[1] or up.shape[0] != lin.weight.shape[0]:
+            raise ValueError(f"ltxmi.lora: '{path}' is [{up.shape[0]}, r] x [r, {down.shape[1]}] but the linear is "
+                             f"{tuple(lin.weight.shape)}")
+
+
+def rebuild(model):
+    """Per-linear state of every block from ``model._lora_adapters`` ({name: [adapter, weight, block entries]}); bumps the epoch."""
+    active = model.__dict__.get("_lora_adapters") or OrderedDict()
+    ep = model.__dict__.get("_lora_epoch", 0) + 1
+    model.__dict__["_lora_epoch"] = ep
+    with torch.no_grad():
+        for i, block in enumerate(model.transformer_blocks):
+            owners = {}
+            for owner_name, slot, members in SLOTS:
+                owner = getattr(block, owner_name, None)
+                if owner is None:
+                    continue
+                slots = owners.setdefault(owner_name, (owner, {}))[1]
+                states = []
+                for m in members:
+                    target = f"{owner_name}.{m}"
+                    entries = []
+                    for adapter, weight, mine in active.values():
+                        path = mine.get((i, target))
+                        if path is not None:
+                            down, up, _ = adapter.modules[path]
+                            entries.append((down, up, adapter.scale(path, weight)))
+                    states.append(_member_state(_get(owner, m), entries) if entries else None)
+                if all(s is None for s in states):
+                    continue
+                R = max(s[0].shape[0] for s in states if s is not None)
+                R = (R + RANK_PAD - 1) // RANK_PAD * RANK_PAD
+                lins = [_get(owner, m) for m in members]
+                if len(members) > 1 and any(l.weight.shape[0] % 128 for l in lins):
+                    raise NotImplementedError("ltxmi.lora: a packed projection takes an adapter only with an inner dimension "
+                                              "that is a multiple of 128")
+                downs, ups = [], []
+                for lin, s in zip(lins, states):
+                    n, k = lin.weight.shape
+                    if s is None:
+                        downs.append(torch.zeros((R, k), dtype=BF16, device=lin.weight.device))
+                        ups.append(torch.zeros((n, R), dtype=BF16, device=lin.weight.device))
+                    else:
+                        downs.append(_pad_to(s[0], rows=R))
+                        ups.append(_pad_to(s[1], cols=R))
+                slots[slot] = LoraSlot(torch.cat(downs, 0).contiguous(), torch.cat(ups, 0).contiguous(),
+                                       lins[0].weight.shape[0] if len(members) > 1 else 0)
+            for owner, slots in owners.values():
+                owner.__dict__["_lora"] = slots or None
+                owner.__dict__["_lora_epoch"] = ep

@@ -155,32 +155,70 @@ def _gemm_args(a, w, bias, out, epilogue, residual, gate_table, gate_temb, rows_
     return args, out, M, N, K
 
 
+def _gemm_pair(M, N, a2, w2, a2_group_cols):
+    """The ltxmi_gemm_pair of a second operand pair: a2 [M, groups * K2] (a row-strided view is fine), w2 [N, K2]."""
+    if w2 is None:
+        raise ValueError("ltxmi.gemm: a2 given without w2")
+    t2, M2, lda2 = _rows(a2)
+    if w2.dim() != 2 or w2.stride(1) != 1:
+        raise ValueError("ltxmi.gemm: w2 must be 2-D with a contiguous innermost dimension")
+    K2 = w2.shape[1]
+    groups = N // a2_group_cols if a2_group_cols > 0 else 1
+    if M2 != M or w2.shape[0] != N or t2.shape[1] != groups * K2:
+        raise ValueError(f"ltxmi.gemm: a2 is [{M2},{t2.shape[1]}], w2 is [{w2.shape[0]},{K2}]: expected [{M},{groups}*K2], [{N},K2]")
+    pair = _lib.GemmPair()
+    pair.A2, pair.lda2 = t2.data_ptr(), lda2
+    pair.W2, pair.ldw2 = w2.data_ptr(), w2.stride(0)
+    pair.K2, pair.group_cols = K2, a2_group_cols
+    return pair
+
+
 def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
-         rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0):
+         rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0,
+         a2=None, w2=None, a2_group_cols=0):
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  ``a``/``out``/``residual`` may be row-strided 2-D views.
-    gate_temb: 2-D view [groups, N] (row stride = gate_ld)."""
-    _chk_bf16(a, w, bias, out, residual, gate_table, gate_temb)
+    gate_temb: 2-D view [groups, N] (row stride = gate_ld).
+    ``a2`` [M, groups * K2], ``w2`` [N, K2]: a second operand pair that continues the K loop (an adapter applied unmerged,
+    ltxmi_gemm_pair2_bf16): out = epi(a @ w^T + a2[:, g K2:(g + 1) K2] @ w2^T + bias) with g = n // a2_group_cols (0: one
+    group).  Without ``a2`` the call is ltxmi_gemm_bf16's."""
+    _chk_bf16(a, w, bias, out, residual, gate_table, gate_temb, a2, w2)
+    if a2 is None and w2 is not None:
+        raise ValueError("ltxmi.gemm: w2 given without a2")
+    if a2 is not None:
+        # checked before anything is allocated or launched: a refused call leaves ``out`` as it was
+        M, N = _rows(a)[1], w.shape[0]
+        pair = _gemm_pair(M, N, a2, w2, a2_group_cols)
     args, out, M, N, K = _gemm_args(a, w, bias, out, epilogue, residual, gate_table, gate_temb, rows_per_group, algo,
                                     rowsumsq, rowsumsq_cols, a_kblock, a_kblock_stride, True)
-    tok = _prof_begin(("gemm", M, N, K, epilogue))
-    check(lib.ltxmi_gemm_bf16(ctypes.byref(args), _stream()), "ltxmi_gemm_bf16")
+    if a2 is None:
+        tok = _prof_begin(("gemm", M, N, K, epilogue))
+        check(lib.ltxmi_gemm_bf16(ctypes.byref(args), _stream()), "ltxmi_gemm_bf16")
+    else:
+        tok = _prof_begin(("gemm_pair2", M, N, K, epilogue))
+        check(lib.ltxmi_gemm_pair2_bf16(ctypes.byref(args), ctypes.byref(pair), _stream()), "ltxmi_gemm_pair2_bf16")
     _prof_end(tok)
     return out
 
 
 GEMM_TILE128, GEMM_TILE256, GEMM_PERSISTENT256 = 0, 1, 2      # include/ltxmi.h: ltxmi_gemm_kernel_id
+GEMM_PAIR2_TILE128, GEMM_PAIR2_TILE256 = 3, 4                  # ... ltxmi_gemm_pair2_kernel_id
 
 
 def gemm_kernel_id(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
-                   rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0):
+                   rows_per_group=1, algo=0, rowsumsq=None, rowsumsq_cols=0, a_kblock=0, a_kblock_stride=0,
+                   a2=None, w2=None, a2_group_cols=0):
     """Which kernel ``gemm`` runs for the same arguments (0 the 128x128 tile kernel, 1 the non-persistent 256x256 one,
-    2 the persistent 256x256 one), or the negative status ``gemm`` would raise on.  Built from the same struct as the
+    2 the persistent 256x256 one; with a second pair 3 the 128x128 two-pair kernel, 4 the 256x256 one), or the negative
+    status ``gemm`` would raise on.  Built from the same struct as the
     launch and decided by the same code; nothing is launched or read, so the tensors may live on any device (only their
     shapes, strides and addresses count)."""
-    _chk_bf16_any_device(a, w, bias, out, residual, gate_table, gate_temb)
+    _chk_bf16_any_device(a, w, bias, out, residual, gate_table, gate_temb, a2, w2)
     args = _gemm_args(a, w, bias, out, epilogue, residual, gate_table, gate_temb, rows_per_group, algo,
                       rowsumsq, rowsumsq_cols, a_kblock, a_kblock_stride, False)[0]
-    return int(lib.ltxmi_gemm_kernel_id(ctypes.byref(args)))
+    if a2 is None:
+        return int(lib.ltxmi_gemm_kernel_id(ctypes.byref(args)))
+    pair = _gemm_pair(args.M, args.N, a2, w2, a2_group_cols)
+    return int(lib.ltxmi_gemm_pair2_kernel_id(ctypes.byref(args), ctypes.byref(pair)))
 
 
 def norm_modulate(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):

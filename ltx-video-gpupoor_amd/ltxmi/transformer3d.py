@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional
 import torch
 from torch import nn
 
-from . import ops
+from . import lora, ops
 from .attention import BasicTransformerBlock, SkipLayerStrategy
 
 BF16 = torch.bfloat16
@@ -154,6 +154,63 @@ class Transformer3DModel(nn.Module):
                           if k.startswith("model.diffusion_model.")}
         return super().load_state_dict(state_dict, *args, **kwargs)
 
+    # ------------------------------------------------------------------ LoRA adapters (ltxmi/lora.py)
+    def attach_lora(self, adapter, weight: float = 1.0, name: Optional[str] = None, strict: bool = True):
+        """Run ``adapter`` (``loading.load_lora``) unmerged on top of the base weights, at strength ``weight``; several
+        adapters may be active at once.  Targets are the ten linears of every block.  An adapter that names another linear
+        (patchify_proj, adaln_single.*, caption_projection.*, proj_out): ``strict=True`` raises and lists them,
+        ``strict=False`` skips them.  Returns the list of skipped linears.  The reference: inference.py:483-493."""
+        mine, other = lora.split_targets(adapter, len(self.transformer_blocks))
+        if other and strict:
+            raise ValueError("ltxmi: the adapter names linears outside the transformer blocks, which carry no adapter here: "
+                             + ", ".join(other))
+        lora.check_shapes(self, adapter, mine)
+        active = self.__dict__.setdefault("_lora_adapters", lora.OrderedDict())
+        if name is None:
+            name = f"lora{len(active)}"
+            while name in active:
+                name += "_"
+        if name in active:
+            raise ValueError(f"ltxmi: an adapter named '{name}' is attached already")
+        active[name] = [adapter, float(weight), mine]
+        try:
+            lora.rebuild(self)
+        except Exception:
+            del active[name]
+            lora.rebuild(self)
+            raise
+        return other
+
+    def set_lora_weights(self, weights: Dict[str, float]):
+        """New strengths for attached adapters, by name; the base weights are not touched."""
+        active = self.__dict__.get("_lora_adapters") or {}
+        for name in weights:
+            if name not in active:
+                raise KeyError(f"ltxmi: no adapter named '{name}' is attached")
+        for name, w in weights.items():
+            active[name][1] = float(w)
+        lora.rebuild(self)
+
+    def detach_lora(self, name: Optional[str] = None):
+        """Detach one adapter, or all of them: the model computes what it computed before ``attach_lora``, bit for bit."""
+        active = self.__dict__.get("_lora_adapters") or {}
+        if name is None:
+            active.clear()
+        elif name not in active:
+            raise KeyError(f"ltxmi: no adapter named '{name}' is attached")
+        else:
+            del active[name]
+        lora.rebuild(self)
+
+    def lora_names(self):
+        return list(self.__dict__.get("_lora_adapters") or {})
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        if self.__dict__.get("_lora_adapters"):
+            lora.rebuild(self)                   # the per-linear state follows the weights' device
+        return out
+
     # ------------------------------------------------------------------ helpers kept verbatim
     def create_skip_layer_mask(self, batch_size: int, num_conds: int, ptb_index: int,
                                skip_block_list: Optional[List[int]] = None):     # transformer3d.py:171-186
@@ -199,6 +256,8 @@ class Transformer3DModel(nn.Module):
         blocks = [b for b in self.transformer_blocks if getattr(b, "attn2", None) is not None]
         if not blocks or ehs.dim() != 3 or not ehs.is_contiguous():
             return
+        if any(lora.has_slot(b.attn2, "kv") for b in blocks):
+            return          # an adapter on a to_k / to_v: the per-layer projections carry it (once per generation)
         packs = [b.attn2.packed_kv() for b in blocks]
         if any(bk is None for _, bk in packs) or len({tuple(w.shape) for w, _ in packs}) != 1:
             return
@@ -216,7 +275,7 @@ class Transformer3DModel(nn.Module):
         for i, b in enumerate(blocks):
             kv = kv_all[:, i * two_d:(i + 1) * two_d]
             ops.rmsnorm_rope_(kv[:, :two_d // 2], b.attn2.k_norm.weight, b.attn2.k_norm.eps)
-            b.attn2.__dict__["_text_kv_ready"] = (ehs, ops.tensor_version(ehs), kv)
+            b.attn2.__dict__["_text_kv_ready"] = (ehs, ops.tensor_version(ehs), kv, lora.epoch(b.attn2))
 
     def _run_blocks_microbatched(self, hidden_states, slices, freqs_cis, attention_mask, encoder_hidden_states,
                                  encoder_attention_mask, temb, cross_attention_kwargs, class_labels, layer_mask,
