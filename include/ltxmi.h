@@ -24,7 +24,9 @@
  *     0.6: lse* of ltxmi_attn_args; 0.7: no field -- ltxmi_gemm_kernel_id, ltxmi_conv3d_route, ltxmi_gemm_args.algo = 256 is honoured for every
  *     shape, and the GEMM entry check refuses a bad epilogue and a residual / gate pointer off an 8-byte boundary;
  *     0.8: no field -- ltxmi_norm_modulate_f32in_bf16 and ltxmi_gate_residual_f32, the row passes of the fp32 residual stream;
- *     0.9: no field -- pad_replicate = 2, and ltxmi_gemm_pair2_bf16 / ltxmi_gemm_pair2_kernel_id with a struct of their own),
+ *     0.9: no field -- pad_replicate = 2, ltxmi_gemm_pair2_bf16 / ltxmi_gemm_pair2_kernel_id with a struct of their own, and the T5
+ *     encoder's entries ltxmi_attention_relbias_bf16 (a struct of its own), ltxmi_rmsnorm_weight_bf16, ltxmi_gated_gelu_bf16,
+ *     ltxmi_embedding_bf16),
  *     and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
  *     switches its companion size / stride fields off whatever they hold.
@@ -627,6 +629,63 @@ int ltxmi_tile_blend(const void* a, void* b, int32_t dtype, int64_t outer, int64
                      int64_t inner, int32_t extent, void* stream);
 int ltxmi_adain_filter(const void* latents, const void* reference, void* out, int32_t is_bf16, int32_t planes,
                        int64_t n, int64_t n_ref, float factor, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * T5-v1.1 text encoder (0.9, appended: no existing struct or entry changes).  The reference holds a bf16 T5-v1.1-XXL encoder (ltx_video/ltxv.py:200-209) and calls it at
+ * pipeline_ltx_video.py:405-417 (prompt) and :449-461 (negative prompt); the arithmetic restated is the eager bf16 forward
+ * of Hugging Face transformers' modeling_t5.py.  Its linears are bias-free and run on ltxmi_gemm_bf16 (the residual adds on
+ * LTXMI_EPI_GATE_RESIDUAL with gate_table == NULL); the four entries below are the rest.
+ * ------------------------------------------------------------------------------- */
+/* Attention with a relative position bias (T5Attention.forward; pipeline_ltx_video.py:405-417):
+ *   O = softmax(softmax_scale * Q K^T + rel_bias[h, j - i] + key_bias[b, j]) V,   i = query, j = key
+ * bf16 in and out, scores and softmax in fp32.  Layout and strides as ltxmi_attn_args (NHD, strides in elements: q, k, v may
+ * be slices of one packed [B, L, 3 * H * 64] projection).
+ * rel_bias: fp32; the value for head h and offset d = j - i is rel_bias[h * rel_stride_h + rel_center + d].  The kernel knows
+ *   nothing of buckets: the caller expands the bucketed table over the offsets once.  rel_center >= Lq - 1 and rel_stride_h >=
+ *   rel_center + Lk (else LTXMI_ERR_INVALID_ARG), so every offset of the call lies inside its head's row.  NULL = no relative
+ *   bias: the call is ltxmi_attention_fwd_bf16's, bit for bit, with the shape limits below.
+ * key_bias: optional fp32 [B, Lk] with the contract of ltxmi_attn_args: a value at or below -1e30 (-inf included) removes the
+ *   key with weight exactly 0; a batch row with every key removed is undefined.
+ * softmax_scale: T5 does not scale its scores and passes 1.0.
+ * The softmax is the textbook max-subtracted one (a query's whole score row is held in registers): T5's unscaled logits reach
+ * hundreds, which the fixed-reference form of the pipelined kernels is not made for.  The row sum is taken over the bf16 P.
+ * head_dim == 64 and 1 <= Lq, Lk <= 512 (else LTXMI_ERR_UNSUPPORTED, nothing is launched); ragged tails are masked inside
+ * the kernel; strides multiples of 8, q / k / v / o 16-byte aligned, the biases 4-byte aligned (else LTXMI_ERR_UNSUPPORTED). */
+typedef struct ltxmi_attn_relbias_args {
+    const void* q; int64_t q_stride_b, q_stride_l;
+    const void* k; int64_t k_stride_b, k_stride_l;
+    const void* v; int64_t v_stride_b, v_stride_l;
+    void*       o; int64_t o_stride_b, o_stride_l;
+    const float* key_bias; int64_t bias_stride_b;   /* NULL = no key bias */
+    int32_t B, H, Lq, Lk, head_dim;
+    float   softmax_scale;
+    const float* rel_bias; int64_t rel_stride_h; int32_t rel_center;   /* NULL = no relative bias */
+} ltxmi_attn_relbias_args;
+int ltxmi_attention_relbias_bf16(const ltxmi_attn_relbias_args* args, void* stream);
+
+/* T5LayerNorm (modeling_t5.py; the norms in front of the attention and the feed-forward of every block and the final norm
+ * behind pipeline_ltx_video.py:405-417), out of place:  y = bf16(bf16(x * rsqrt(mean(x^2) + eps)) * weight).
+ * The statistics and the first product are fp32; the product is rounded to the weight's dtype and the multiply by the weight
+ * rounds again, as the module does.  One wave per row; the squares are added in a fixed order (per lane its 16-byte chunks in
+ * turn, then a wave butterfly) and sum / D, + eps, sqrt and the reciprocal are each a correctly rounded fp32 operation.  D % 8 == 0, D <= 8192, ldx, ldy % 8 == 0 and >= D,
+ * x / y / weight 16-byte aligned, rows <= 4 * (2^24 - 1) (one launch of fewer than 2^32 threads) (else LTXMI_ERR_UNSUPPORTED and
+ * nothing is written).  y must not overlap x. */
+int ltxmi_rmsnorm_weight_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t D,
+                              const void* weight, float eps, void* stream);
+
+/* T5DenseGatedActDense's activation (feed_forward_proj = "gated-gelu"; pipeline_ltx_video.py:405-417) over the output h
+ * [rows, 2F] of ONE GEMM against the stacked [wi_0; wi_1]:
+ *   y[r, c] = bf16(bf16(gelu_tanh(h[r, c])) * h[r, F + c]),   c < F
+ * (`hidden_gelu = act(wi_0(x))` is a bf16 tensor, the product with `wi_1(x)` rounds again).  F % 8 == 0, ldh % 8 == 0 and
+ * >= 2F, ldy % 8 == 0 and >= F, h and y 16-byte aligned (else LTXMI_ERR_UNSUPPORTED); 16-byte accesses, grid-stride. */
+int ltxmi_gated_gelu_bf16(const void* h, int64_t ldh, void* y, int64_t ldy, int32_t rows, int32_t F, void* stream);
+
+/* nn.Embedding lookup (T5Stack.embed_tokens; pipeline_ltx_video.py:405-417):  out[r, :] = table[ids[r], :].
+ * ids: int64 on the device, as the tokenizer hands them over.  A row whose id is outside [0, vocab) is written as zeros: no
+ * id is turned into an address before it has been checked.  D % 8 == 0, ld_table, ldo % 8 == 0 and >= D, table and out
+ * 16-byte aligned, rows <= 2^24 - 1 (one workgroup per row, fewer than 2^32 threads per launch) (else LTXMI_ERR_UNSUPPORTED). */
+int ltxmi_embedding_bf16(const int64_t* ids, const void* table, int64_t ld_table, int64_t vocab, void* out, int64_t ldo,
+                         int32_t rows, int32_t D, void* stream);
 
 #ifdef __cplusplus
 }

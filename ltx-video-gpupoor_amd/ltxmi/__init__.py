@@ -15,6 +15,7 @@ from .pipeline import ConditioningItem, LTXMultiScalePipeline, LTXVideoPipeline,
 from .latent_upsampler import LatentUpsampler, adain_filter_latent, upsample_latents  # noqa: F401
 from .scheduler import RectifiedFlowScheduler  # noqa: F401
 from .transformer3d import Transformer3DModel, Transformer3DModelOutput  # noqa: F401
+from .t5 import T5Config, T5EncoderModel  # noqa: F401
 
 __version__ = _lib.lib.ltxmi_version().decode()
 from .ops import set_step_invariant_caching  # noqa: E402,F401

@@ -49,6 +49,17 @@ class AttnArgs(ctypes.Structure):
                 ("lse", c_void_p), ("lse_stride_b", c_int64), ("lse_stride_h", c_int64)]
 
 
+class AttnRelBiasArgs(ctypes.Structure):
+    _fields_ = [("q", c_void_p), ("q_stride_b", c_int64), ("q_stride_l", c_int64),
+                ("k", c_void_p), ("k_stride_b", c_int64), ("k_stride_l", c_int64),
+                ("v", c_void_p), ("v_stride_b", c_int64), ("v_stride_l", c_int64),
+                ("o", c_void_p), ("o_stride_b", c_int64), ("o_stride_l", c_int64),
+                ("key_bias", c_void_p), ("bias_stride_b", c_int64),
+                ("B", c_int), ("H", c_int), ("Lq", c_int), ("Lk", c_int), ("head_dim", c_int),
+                ("softmax_scale", c_float),
+                ("rel_bias", c_void_p), ("rel_stride_h", c_int64), ("rel_center", c_int)]
+
+
 ATTN_MERGE_MAX = 8
 
 
@@ -145,6 +156,10 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p]),
     "ltxmi_guidance_step_bf16": (c_int, [c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_int, c_int,
                                          c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "ltxmi_attention_relbias_bf16": (c_int, [ctypes.POINTER(AttnRelBiasArgs), c_void_p]),
+    "ltxmi_rmsnorm_weight_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_float, c_void_p]),
+    "ltxmi_gated_gelu_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "ltxmi_embedding_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p]),
 }
 
 

@@ -223,3 +223,56 @@ def load_vae(path, device="cuda", dtype=torch.bfloat16, with_encoder=True):
         raise KeyError(f"checkpoint is missing VAE tensors: {missing[:5]} ...")
     vae.load_state_dict({k: v for k, v in sd.items() if k in want}, strict=True)
     return vae.to(device=device, dtype=dtype).eval()
+
+
+T5_PREFIXES = ("text_encoder.", "t5.", "model.")
+
+
+def load_t5_encoder(path_or_state_dict, config, device="cuda", dtype=torch.bfloat16):
+    """``t5.T5EncoderModel`` from a safetensors file (or a state dict) and its config (a dict, or the path of a
+    ``T5_config.json``): what ltxv.py:200-209 does with ``T5_xxl_1.1_enc_bf16.safetensors``.
+
+    Fields read from the config: d_model, d_kv, d_ff, num_heads, num_layers, vocab_size, relative_attention_num_buckets,
+    relative_attention_max_distance, layer_norm_epsilon, feed_forward_proj.  Keys are Hugging Face's T5EncoderModel names
+    (``shared.weight``, ``encoder.block.N.layer.0.SelfAttention.q.weight``, ...; ``encoder.embed_tokens.weight`` is an alias
+    of ``shared.weight``), with the prefixes ``text_encoder.``, ``t5.``, ``model.`` or none stripped.  Every encoder tensor
+    must be there; keys that name nothing in the encoder (a full T5's ``decoder.*`` and ``lm_head.weight``) are skipped and
+    returned as ``model.unexpected_keys``.  Tensors are cast to ``dtype`` and go straight to ``device``; the stacked ``[q; k; v]``
+    and ``[wi_0; wi_1]`` GEMM operands are built here, once, and the five weights are views of them (no second copy)."""
+    from .t5 import T5Config, T5EncoderModel
+    if isinstance(config, (str, os.PathLike)):
+        with open(config) as f:
+            config = json.load(f)
+    cfg = T5Config(config)
+    if isinstance(path_or_state_dict, dict):
+        sd = dict(path_or_state_dict)
+    else:
+        path = str(path_or_state_dict)
+        if not path.endswith(".safetensors"):
+            raise ValueError(f"ltxmi.load_t5_encoder: only safetensors files are read, got {path}")
+        sd, _ = _read_safetensors(path, device)
+    with torch.device("meta"):
+        model = T5EncoderModel(cfg)
+    want = set(model.state_dict()) | {"encoder.embed_tokens.weight"}
+    kept, unexpected = {}, []
+    for key, t in sd.items():
+        k = key
+        for pre in T5_PREFIXES:
+            if k.startswith(pre) and k[len(pre):] in want:
+                k = k[len(pre):]
+                break
+        if k in want:
+            kept[k] = t.to(device=device, dtype=dtype)
+        else:
+            unexpected.append(key)
+    missing = [k for k in model.state_dict() if k not in kept and not (k == "shared.weight" and "encoder.embed_tokens.weight" in kept)]
+    if missing:
+        raise KeyError(f"ltxmi.load_t5_encoder: the checkpoint is missing encoder tensors: {missing[:5]}{' ...' if len(missing) > 5 else ''}")
+    model.load_state_dict(kept, strict=True, assign=True)
+    del kept
+    for block in model.encoder.block:
+        # the stacked [q; k; v] and [wi_0; wi_1] GEMM operands, built once; q, k, v, wi_0, wi_1 become views of them
+        block.layer[0].SelfAttention.share_packed()
+        block.layer[1].DenseReluDense.share_packed()
+    model.unexpected_keys = sorted(unexpected)
+    return model.eval()

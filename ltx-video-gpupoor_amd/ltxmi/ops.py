@@ -970,3 +970,103 @@ def tile_blend_(a, b, extent, dim):
     check(lib.ltxmi_tile_blend(_ptr(a), _ptr(b), codes[b.dtype], outer, sa[dim], sb[dim], inner, extent, _stream()),
           "ltxmi_tile_blend")
     return b
+
+
+# ---- T5 text encoder (ltxmi/t5.py) ------------------------------------------------------------------------------------
+def attention_relbias(q, k, v, rel_bias=None, rel_center=0, key_bias=None, softmax_scale=1.0, out=None):
+    """softmax(softmax_scale q k^T + rel_bias[h, j - i] + key_bias[b, j]) v -- T5's attention (ltxmi_attention_relbias_bf16).
+    q [B, Lq, H, 64], k / v [B, Lk, H, 64] as ``attention`` takes them (slices of one packed projection are fine).
+    rel_bias: fp32 [H, >= rel_center + Lk], the value for head h and offset d = key - query at ``rel_bias[h, rel_center +
+    d]``, rel_center >= Lq - 1; None: no relative bias, the call is ``attention``'s.  key_bias: fp32 [B, Lk] with the
+    contract of ``attention`` (at or below -1e30 removes the key).  T5 does not scale its scores: softmax_scale = 1."""
+    _chk_bf16(q, k, v, out)
+    B, Lq, H, dh = q.shape
+    Lk = k.shape[1]
+    for t in (q, k, v):
+        if t.stride(3) != 1 or t.stride(2) != dh:
+            raise ValueError("ltxmi.attention_relbias: (heads, head_dim) must be contiguous")
+    if out is None:
+        out = torch.empty((B, Lq, H, dh), dtype=BF16, device=q.device)
+    if tuple(out.shape) != (B, Lq, H, dh) or out.stride(3) != 1 or out.stride(2) != dh:
+        raise ValueError(f"ltxmi.attention_relbias: out must be [B, Lq, H, dh] = {(B, Lq, H, dh)} with (heads, head_dim) contiguous")
+    a = _lib.AttnRelBiasArgs()
+    a.q, a.q_stride_b, a.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
+    a.k, a.k_stride_b, a.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
+    a.v, a.v_stride_b, a.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
+    a.o, a.o_stride_b, a.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    if key_bias is not None:
+        if key_bias.dtype != torch.float32 or key_bias.shape != (B, Lk) or key_bias.stride(1) != 1 or not key_bias.is_cuda:
+            raise ValueError("ltxmi.attention_relbias: key_bias must be a CUDA fp32 [B, Lk]")
+        a.key_bias, a.bias_stride_b = key_bias.data_ptr(), key_bias.stride(0)
+    if rel_bias is not None:
+        if rel_bias.dtype != torch.float32 or rel_bias.dim() != 2 or rel_bias.shape[0] != H or rel_bias.stride(1) != 1 \
+                or not rel_bias.is_cuda or rel_bias.shape[1] < rel_center + Lk:
+            raise ValueError("ltxmi.attention_relbias: rel_bias must be a CUDA fp32 [H, >= rel_center + Lk]")
+        a.rel_bias, a.rel_stride_h, a.rel_center = rel_bias.data_ptr(), rel_bias.stride(0), rel_center
+    a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, dh
+    a.softmax_scale = float(softmax_scale)
+    tok = _prof_begin(("attention_relbias", B, H, Lq, Lk, dh))
+    check(lib.ltxmi_attention_relbias_bf16(ctypes.byref(a), _stream()), "ltxmi_attention_relbias_bf16")
+    _prof_end(tok)
+    return out
+
+
+def rmsnorm_weight(x, weight, eps, out=None):
+    """T5LayerNorm, out of place: bf16(bf16(x * rsqrt(mean(x^2) + eps)) * weight).  x: [..., D] rows (row-strided 2-D views
+    are fine); ``out`` must not overlap x."""
+    _chk_bf16(x, weight, out)
+    x2, rows, ldx = _rows(x)
+    D = x2.shape[1]
+    if weight.shape != (D,) or weight.stride(0) != 1:
+        raise ValueError(f"ltxmi.rmsnorm_weight: weight must be a contiguous [{D}]")
+    if out is None:
+        out = torch.empty(x.shape, dtype=BF16, device=x.device)
+    o2, orows, ldy = _rows(out)
+    if orows != rows or o2.shape[1] != D:
+        raise ValueError("ltxmi.rmsnorm_weight: out must have x's rows and channels")
+    tok = _prof_begin(("rmsnorm_weight", rows, D))
+    check(lib.ltxmi_rmsnorm_weight_bf16(_ptr(x2), ldx, _ptr(o2), ldy, rows, D, _ptr(weight), float(eps), _stream()),
+          "ltxmi_rmsnorm_weight_bf16")
+    _prof_end(tok)
+    return out
+
+
+def gated_gelu(h, out=None):
+    """h [rows, 2F] (the output of one GEMM against the stacked [wi_0; wi_1]) -> [rows, F]:
+    bf16(bf16(gelu_tanh(h[:, :F])) * h[:, F:])."""
+    _chk_bf16(h, out)
+    h2, rows, ldh = _rows(h)
+    if h2.shape[1] % 2:
+        raise ValueError("ltxmi.gated_gelu: h must be [rows, 2F]")
+    F = h2.shape[1] // 2
+    if out is None:
+        out = torch.empty((*h.shape[:-1], F), dtype=BF16, device=h.device)
+    o2, orows, ldy = _rows(out)
+    if orows != rows or o2.shape[1] != F:
+        raise ValueError("ltxmi.gated_gelu: out must be [rows, F]")
+    tok = _prof_begin(("gated_gelu", rows, F))
+    check(lib.ltxmi_gated_gelu_bf16(_ptr(h2), ldh, _ptr(o2), ldy, rows, F, _stream()), "ltxmi_gated_gelu_bf16")
+    _prof_end(tok)
+    return out
+
+
+def embedding(ids, table, out=None):
+    """table[ids]: ids int64 on the device (any shape), table bf16 [vocab, D] -> [*ids.shape, D].  A row whose id is
+    outside [0, vocab) comes back as zeros."""
+    _chk_bf16(table, out)
+    if ids.dtype != torch.int64 or not ids.is_cuda:
+        raise TypeError(f"ltxmi.embedding: ids must be a CUDA int64 tensor, got {ids.dtype} on {ids.device}")
+    if table.dim() != 2 or table.stride(1) != 1:
+        raise ValueError("ltxmi.embedding: table must be [vocab, D] with a contiguous innermost dimension")
+    flat = ids.reshape(-1).contiguous()
+    vocab, D = table.shape
+    if out is None:
+        out = torch.empty((*ids.shape, D), dtype=BF16, device=table.device)
+    o2, orows, ldo = _rows(out)
+    if orows != flat.numel() or o2.shape[1] != D:
+        raise ValueError("ltxmi.embedding: out must be [*ids.shape, D]")
+    tok = _prof_begin(("embedding", flat.numel(), D))
+    check(lib.ltxmi_embedding_bf16(_ptr(flat), _ptr(table), table.stride(0), vocab, _ptr(o2), ldo, flat.numel(), D, _stream()),
+          "ltxmi_embedding_bf16")
+    _prof_end(tok)
+    return out

@@ -137,8 +137,9 @@ class LTXVideoPipeline:
         (embeds (n, num_tokens, d) in ``dtype``, attention mask (n, num_tokens)), both on ``device``."""
         if self.text_encoder is None or self.tokenizer is None:
             raise RuntimeError("ltxmi.LTXVideoPipeline.encode_prompt: text prompts (the negative one included) need the "
-                               "caller's T5 (`tokenizer=` and `text_encoder=` at construction) -- the text encoder is outside "
-                               "this library; alternatively pass the embeddings and their attention masks")
+                               "caller's T5 (`tokenizer=` and `text_encoder=` at construction; `ltxmi.T5EncoderModel` / "
+                               "`ltxmi.loading.load_t5_encoder` is this library's encoder, the tokenizer is the caller's); "
+                               "alternatively pass the embeddings and their attention masks")
         t5_device = next(self.text_encoder.parameters()).device
         tokens = self.tokenizer([text.strip() for text in texts], padding="max_length", max_length=num_tokens,
                                 truncation=True, add_special_tokens=True, return_tensors="pt")
