@@ -10,6 +10,20 @@ __device__ __forceinline__ void add_bf16x4(V&& v, u32x2 w) {
     v[0] += bf_lo(w[0]); v[1] += bf_hi(w[0]);
     v[2] += bf_lo(w[1]); v[3] += bf_hi(w[1]);
 }
+// v + a + b with the association written down.  Left to -ffast-math, hipcc picks one per kernel instance (two add_bf16x4 in a row
+// came out as v + (a + b) in one instance and (v + a) + b in another of the same source): one bf16 ulp in a few values per
+// million after the rounding, where the two-pair kernel owes the bits of the plain GEMM on the concatenation.
+template <bool OPERANDS_FIRST, class V>
+__device__ __forceinline__ void add2_bf16x4(V&& v, u32x2 a, u32x2 b) {
+#pragma clang fp reassociate(off)
+    if (OPERANDS_FIRST) {
+        v[0] = v[0] + (bf_lo(a[0]) + bf_lo(b[0])); v[1] = v[1] + (bf_hi(a[0]) + bf_hi(b[0]));
+        v[2] = v[2] + (bf_lo(a[1]) + bf_lo(b[1])); v[3] = v[3] + (bf_hi(a[1]) + bf_hi(b[1]));
+    } else {
+        v[0] = (v[0] + bf_lo(a[0])) + bf_lo(b[0]); v[1] = (v[1] + bf_hi(a[0])) + bf_hi(b[0]);
+        v[2] = (v[2] + bf_lo(a[1])) + bf_lo(b[1]); v[3] = (v[3] + bf_hi(a[1])) + bf_hi(b[1]);
+    }
+}
 template <class V>
 __device__ __forceinline__ void mul_sum_bf16x4(V&& v, u32x2 a, u32x2 b) {      // v *= a + b
     v[0] *= bf_lo(a[0]) + bf_lo(b[0]); v[1] *= bf_hi(a[0]) + bf_hi(b[0]);
@@ -19,7 +33,8 @@ template <class V>
 __device__ __forceinline__ u32x2 pack_bf16x4(V&& v) {
     return u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
 }
-// ---- the dense GEMMs' internal epilogues, beside the public ltxmi_epilogue values (gemm.hip, gemm_pair2.hip)
+// ---- the GEMMs' internal epilogues, beside the public ltxmi_epilogue values (gemm.hip, gemm_pair2.hip)
+constexpr int EPI_D2S = 4;        // internal: conv + pixel-shuffle(2,2,2) scatter (+ residual)
 constexpr int EPI_RESIDUAL = 5;   // internal: GATE_RESIDUAL without a gate (C = R + acc + bias)
 constexpr int EPI_SUMSQ = 6;      // internal: plain store + per-(row, 64-column block) sum of squares of the stored bf16
                                   // values for the columns < sumsq_cols (the q part of a fused QKV projection: the

@@ -24,52 +24,12 @@
 // Block -> tile mapping is XCD-aware: the 8 XCDs each get a contiguous band of M-tiles so
 // the W panel and the A rows they share stay in that XCD's private L2.
 #include "conv.h"
-#include "epilogue.h"
+#include "gemm_tile.h"
 
 namespace ltxmi {
 
-struct GemmParams {
-    const uint16_t* A; int64_t lda;
-    const uint16_t* W; int64_t ldw;
-    const uint16_t* bias; int bias_stride;   // never NULL: a zero page with stride 0 stands in for "no bias"
-    uint16_t* C; int64_t ldc;
-    int M, N, K;
-    const uint16_t* R; int64_t ldr;
-    const uint16_t* gate_table;
-    const uint16_t* gate_temb;
-    int64_t gate_ld;
-    int rows_per_group;
-    int tiles_m, tiles_n;
-    // implicit-GEMM convolution (MODE == 1): A rows are gathered from x [B,T,H,W,Cin]
-    int cB, cT, cH, cW, cCin;      // input grid
-    int oT, oH, oW;                 // output grid (== input grid unless strided / extended in time)
-    int sT, sHW;                    // strides (1 or 2)
-    int tzero;                      // time padding with zeros (plain nn.Conv3d) instead of frame replication
-    int tpad;            // frames replicated in front (2 causal, 1 otherwise)
-    int pad_replicate;   // spatial padding mode
-    // depth-to-space epilogue (EPI == EPI_D2S)
-    const uint16_t* res; int res_ch;
-    // EPI_SUMSQ: fp32 [M, sumsq_ld] partial row sums of squares of the bf16 outputs, one per 64-column block
-    float* sumsq; int sumsq_cols; int64_t sumsq_ld;
-    // A whose K axis is cut into blocks of a_kblk elements lying a_kblk_stride elements apart (0 = plain): the receive
-    // buffer of the Ulysses return all-to-all, [P source ranks][rows][D / P], is consumed in place by to_out
-    int a_kblk; int64_t a_kblk_stride;
-
-    __device__ __forceinline__ int64_t a_koff_elems(int kk) const { // element offset of column kk inside a row of A
-        if (a_kblk <= 0) return kk;
-        const int blk = kk / a_kblk;
-        return (int64_t)blk * a_kblk_stride + (kk - blk * a_kblk);
-    }
-    __device__ __forceinline__ int64_t a_koff(int kt) const { return a_koff_elems(kt * 64); }   // ... of k-tile kt
-};
-
-constexpr int EPI_D2S = 4;   // internal: conv + pixel-shuffle(2,2,2) scatter (+ residual)
-// (EPI_RESIDUAL, EPI_SUMSQ and sumsq4: epilogue.h, shared with gemm_pair2.hip)
-
 // 64 zero bytes: LDS-DMA source for zero-padded taps
 __device__ __attribute__((aligned(16))) uint32_t g_zero_page[16];
-
-constexpr int BK = 64;
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI, int MODE>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(GemmParams p) {
@@ -257,98 +217,8 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_kernel(Gem
         }
     }
 
-    // ---- epilogue.  acc[i][j][e]: row m = m0 + wm*WM + i*16 + (lane&15),
-    //                               col n = n0 + wn*WN + j*16 + (lane>>4)*4 + e
-    // Every load below is unconditional (masked lanes read a clamped address): a runtime-conditional
-    // load makes hipcc branch around it and wait vmcnt(0) per element -- 32 dependent L2 round trips.
-    const int erow = lane & 15;
-    const int ecol = (lane >> 4) * 4;
-    constexpr bool GATED = (EPI == LTXMI_EPI_GATE_RESIDUAL);
-    constexpr bool RESID = (EPI == LTXMI_EPI_GATE_RESIDUAL || EPI == EPI_RESIDUAL);
-    u32x2 bias_v[NI], gt_v[NI];
-    int ncl[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn * WN + j * 16 + ecol;
-        ncl[j] = n < p.N ? n : p.N - 4;
-        bias_v[j] = *(const u32x2*)(p.bias + ncl[j] * p.bias_stride);
-        if (GATED) gt_v[j] = *(const u32x2*)(p.gate_table + ncl[j]);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-        const int m = m0 + wm * WM + i * 16 + erow;
-        const bool m_ok = m < p.M;
-        const int mc = m_ok ? m : p.M - 1;
-        const uint16_t* gate_row = GATED ? p.gate_temb + (int64_t)(mc / p.rows_per_group) * p.gate_ld : nullptr;
-        float ss[NI / 4 > 0 ? NI / 4 : 1];                       // EPI_SUMSQ: one partial per 64 columns (4 fragments)
-#pragma unroll
-        for (int q = 0; q < (NI / 4 > 0 ? NI / 4 : 1); ++q) ss[q] = 0.f;
-        u32x2 ge_v[NI], rr_v[NI];
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            if (GATED) ge_v[j] = *(const u32x2*)(gate_row + ncl[j]);
-            if (RESID) rr_v[j] = *(const u32x2*)(p.R + (int64_t)mc * p.ldr + ncl[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int n = n0 + wn * WN + j * 16 + ecol;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            add_bf16x4(v, bias_v[j]);
-            if (EPI == LTXMI_EPI_GELU_TANH) {
-                // the packed form of the persistent kernel: every GEMM kernel produces the same bits for a given row
-                // (the accumulation order over K is the same in all of them), whatever M made the dispatcher choose
-                gelu_tanh_pk(v[0], v[1]);
-                gelu_tanh_pk(v[2], v[3]);
-            } else if (EPI == LTXMI_EPI_SILU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
-            }
-            if (GATED) {
-                mul_sum_bf16x4(v, gt_v[j], ge_v[j]);
-            }
-            if (RESID) {
-                add_bf16x4(v, rr_v[j]);
-            }
-            if (!(m_ok && n < p.N)) continue;
-            u32x2 o;
-            if (EPI == EPI_D2S) {
-                // weight rows are packed (p1 p2 p3)-major: n = pp * C' + c'
-                const int Cp = p.N >> 3;
-                const int pp = n / Cp, cp = n - pp * Cp;
-                const int x_ = m % p.cW, r1 = m / p.cW, y_ = r1 % p.cH, r2 = r1 / p.cH;
-                const int t_ = r2 % p.cT, b_ = r2 / p.cT;
-                const int to = 2 * t_ + (pp >> 2) - 1;
-                if (to < 0) continue;                       // first upsampled frame is dropped
-                const int yo = 2 * y_ + ((pp >> 1) & 1), xo = 2 * x_ + (pp & 1);
-                if (p.res) {
-                    // x_in = repeat(pixel_shuffle(x)): channel c' <- x[(c' mod (Cres/8)) * 8 + pp]
-                    const uint16_t* rrow = p.res + (int64_t)m * p.res_ch + pp;
-                    const int cm = p.res_ch >> 3;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += bf2f(rrow[((cp + e) % cm) * 8]);
-                }
-                o = pack_bf16x4(v);
-                const int64_t opos = (((int64_t)b_ * (2 * p.cT - 1) + to) * (2 * p.cH) + yo) * (2 * p.cW) + xo;
-                *(u32x2*)(p.C + opos * Cp + cp) = o;
-                continue;
-            }
-            o = pack_bf16x4(v);
-            *(u32x2*)(p.C + (int64_t)m * p.ldc + n) = o;
-            if (EPI == EPI_SUMSQ)
-                ss[j / 4] = sumsq4(ss[j / 4], o);
-        }
-        if (EPI == EPI_SUMSQ) {
-            static_assert(EPI != EPI_SUMSQ || NI % 4 == 0, "sum-of-squares partials are per 64 columns");
-#pragma unroll
-            for (int q = 0; q < NI / 4; ++q) {
-                float s = ss[q];
-                s += __shfl_xor(s, 16, 64);
-                s += __shfl_xor(s, 32, 64);
-                const int nb = n0 + wn * WN + q * 64;            // first column of this 64-column block
-                if (lane < 16 && m_ok && nb < p.sumsq_cols) p.sumsq[(int64_t)m * p.sumsq_ld + (nb >> 6)] = s;
-            }
-        }
-    }
+    // ---- epilogue (gemm_tile.h, shared with gemm_pair2.hip)
+    tile_epilogue<EPI, residual_joins_bias_first(BM)>(epi_args(p), acc, m0 + wm * WM, n0 + wn * WN, lane & 15, (lane >> 4) * 4);
 }
 
 // =====================================================================================
@@ -841,15 +711,7 @@ static int launch_tile(const GemmParams& p0, int epi, hipStream_t stream, const 
                                                                                                     stream, what);
     };
     if constexpr (MODE == 0) {
-        switch (epi) {
-            case LTXMI_EPI_NONE: return go(epi_t<LTXMI_EPI_NONE>{});
-            case EPI_SUMSQ: return go(epi_t<EPI_SUMSQ>{});
-            case LTXMI_EPI_GELU_TANH: return go(epi_t<LTXMI_EPI_GELU_TANH>{});
-            case LTXMI_EPI_SILU: return go(epi_t<LTXMI_EPI_SILU>{});
-            case LTXMI_EPI_GATE_RESIDUAL: return go(epi_t<LTXMI_EPI_GATE_RESIDUAL>{});
-            case EPI_RESIDUAL: return go(epi_t<EPI_RESIDUAL>{});
-            default: set_error("%s: bad epilogue %d", what, epi); return LTXMI_ERR_INVALID_ARG;
-        }
+        return dispatch_epilogue(epi, go, what);
     } else {
         if (epi == EPI_D2S) return go(epi_t<EPI_D2S>{});
         if (epi == EPI_RESIDUAL) return go(epi_t<EPI_RESIDUAL>{});
@@ -869,21 +731,14 @@ static int launch_persistent(const GemmParams& p0, int epi, hipStream_t stream, 
     constexpr int threads = WAVES_M * WAVES_N * 64;
     constexpr int smem = 2 * (BM + BN) * BK * 2 + WAVES_M * WAVES_N * 4096;   // 2 stages + epilogue scratch
     auto go = [&](auto e) {
-        return launch_with_lds<gemm_bf16_nt_persistent_kernel<BM, BN, WAVES_M, WAVES_N, decltype(e)::value>>(p, dim3(grid), dim3(threads),
-                                                                                                     smem, stream, what);
-    };
-    switch (epi) {
         // the plain epilogue runs on the row-sums instance with the sums switched off (sumsq_cols = 0: its extra stores
         // carry an out-of-range offset and are dropped): same bits, and measured 3-6 % faster than a dedicated instance,
-        // which hipcc happens to allocate worst of all (55 spilled VGPRs)
-        case LTXMI_EPI_NONE:
-        case EPI_SUMSQ: return go(epi_t<EPI_SUMSQ>{});
-        case LTXMI_EPI_GELU_TANH: return go(epi_t<LTXMI_EPI_GELU_TANH>{});
-        case LTXMI_EPI_SILU: return go(epi_t<LTXMI_EPI_SILU>{});
-        case LTXMI_EPI_GATE_RESIDUAL: return go(epi_t<LTXMI_EPI_GATE_RESIDUAL>{});
-        case EPI_RESIDUAL: return go(epi_t<EPI_RESIDUAL>{});
-        default: set_error("%s: bad epilogue %d", what, epi); return LTXMI_ERR_INVALID_ARG;
-    }
+        // which hipcc happens to allocate worst of all (55 spilled VGPRs) -- so no plain instance exists
+        constexpr int E = decltype(e)::value == LTXMI_EPI_NONE ? EPI_SUMSQ : decltype(e)::value;
+        return launch_with_lds<gemm_bf16_nt_persistent_kernel<BM, BN, WAVES_M, WAVES_N, E>>(p, dim3(grid), dim3(threads), smem, stream,
+                                                                                            what);
+    };
+    return dispatch_epilogue(epi, go, what);
 }
 
 // device address of the zero page of the CURRENT device (stands in for a missing bias with stride 0); a __device__
@@ -903,11 +758,11 @@ static const uint16_t* zero_page_ptr() {
     return (const uint16_t*)d;
 }
 
-// what the dense call and the convolution have in common: operands, output, shape; everything else of *p stays as the caller's
-// `GemmParams p = {}` left it (the dense call used to set the convolution's grid and strides to 1: they are read under MODE == 1 and
-// EPI_D2S only, which no dense launch instantiates).  A missing bias is the zero page with stride 0.
-static int gemm_params(GemmParams* p, const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc,
-                       int M, int N, int K, const char* what) {
+// Operands, output and shape, which the dense call and the convolution have in common (declared in gemm_tile.h); a missing
+// bias becomes the zero page with stride 0.  The rest of *p stays zero: the convolution's grid and strides are read under
+// MODE == 1 and EPI_D2S only, which no dense launch instantiates.
+int gemm_params(GemmParams* p, const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C, int64_t ldc, int M,
+                int N, int K, const char* what) {
     p->A = (const uint16_t*)A; p->lda = lda;
     p->W = (const uint16_t*)W; p->ldw = ldw;
     p->bias = bias ? (const uint16_t*)bias : zero_page_ptr();
@@ -916,6 +771,23 @@ static int gemm_params(GemmParams* p, const void* A, int64_t lda, const void* W,
     p->C = (uint16_t*)C; p->ldc = ldc;
     p->M = M; p->N = N; p->K = K;
     p->rows_per_group = 1;
+    return LTXMI_OK;
+}
+
+int gemm_dense_params(GemmParams* p, int* epi, const ltxmi_gemm_args* a, const char* what) {
+    if (const int rc = gemm_params(p, a->A, a->lda, a->W, a->ldw, a->bias, a->C, a->ldc, a->M, a->N, a->K, what)) return rc;
+    p->R = (const uint16_t*)a->residual; p->ldr = a->ldr;
+    p->gate_table = (const uint16_t*)a->gate_table;
+    p->gate_temb = (const uint16_t*)a->gate_temb;
+    p->gate_ld = a->gate_ld;
+    if (a->rows_per_group > 0) p->rows_per_group = a->rows_per_group;
+    // without a rowsumsq pointer the cols / ld fields are NOT read: the plain epilogue runs on the row-sums instance and
+    // must see cols = 0 (its extra stores are then dropped) whatever a caller left in those fields
+    p->sumsq = a->rowsumsq;
+    p->sumsq_cols = a->rowsumsq ? a->rowsumsq_cols : 0;
+    p->sumsq_ld = a->rowsumsq ? a->rowsumsq_ld : 0;
+    p->a_kblk = a->a_kblock; p->a_kblk_stride = a->a_kblock_stride;
+    *epi = a->rowsumsq ? EPI_SUMSQ : ((a->epilogue == LTXMI_EPI_GATE_RESIDUAL && !a->gate_table) ? EPI_RESIDUAL : a->epilogue);
     return LTXMI_OK;
 }
 
@@ -1024,21 +896,9 @@ extern "C" int ltxmi_gemm_bf16(const ltxmi_gemm_args* a, void* stream) {
     const int kernel = gemm_plan(a, "ltxmi_gemm_bf16");
     if (kernel < 0) return kernel;
     GemmParams p = {};
-    if (const int rc = gemm_params(&p, a->A, a->lda, a->W, a->ldw, a->bias, a->C, a->ldc, a->M, a->N, a->K, "ltxmi_gemm_bf16")) return rc;
-    p.R = (const uint16_t*)a->residual; p.ldr = a->ldr;
-    p.gate_table = (const uint16_t*)a->gate_table;
-    p.gate_temb = (const uint16_t*)a->gate_temb;
-    p.gate_ld = a->gate_ld;
-    if (a->rows_per_group > 0) p.rows_per_group = a->rows_per_group;
-    // without a rowsumsq pointer the cols / ld fields are NOT read: the plain epilogue runs on the row-sums instance and
-    // must see cols = 0 (its extra stores are then dropped) whatever a caller left in those fields
-    p.sumsq = a->rowsumsq;
-    p.sumsq_cols = a->rowsumsq ? a->rowsumsq_cols : 0;
-    p.sumsq_ld = a->rowsumsq ? a->rowsumsq_ld : 0;
-    p.a_kblk = a->a_kblock; p.a_kblk_stride = a->a_kblock_stride;
+    int epi = 0;
+    if (const int rc = gemm_dense_params(&p, &epi, a, "ltxmi_gemm_bf16")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int epi = a->rowsumsq ? EPI_SUMSQ
-                                : ((a->epilogue == LTXMI_EPI_GATE_RESIDUAL && !a->gate_table) ? EPI_RESIDUAL : a->epilogue);
     switch (kernel) {
         case GEMM_PERSISTENT256: return launch_persistent<256, 256, 2, 4>(p, epi, s, "ltxmi_gemm_bf16");
         case GEMM_TILE256: return launch_tile<256, 256, 2, 4, 0>(p, epi, s, "ltxmi_gemm_bf16");

@@ -16,33 +16,21 @@
 // num_records = its valid rows) plus ONE 32-bit per-lane offset per operand: the two pairs have different pitches, so that is
 // four offset VGPRs, and which pair a K-tile comes from is a wave-uniform select of descriptor, offset and step.  Rows past
 // M / N are out of range for the descriptor and arrive as zeros.
-#include "epilogue.h"
+#include "gemm_tile.h"
 
 namespace ltxmi {
 
 struct Pair2Params {
-    const uint16_t* A; int64_t lda;
-    const uint16_t* W; int64_t ldw;
+    GemmParams g;                            // the first pair, the output and the epilogue's operands, as ltxmi_gemm_bf16 fills them
     const uint16_t* A2; int64_t lda2;
     const uint16_t* W2; int64_t ldw2;
-    const uint16_t* bias; int has_bias;      // never NULL: without a bias it points at W (readable) and has_bias = 0
-    uint16_t* C; int64_t ldc;
-    int M, N, K, K2;
+    int K2;
     int group_cols;                          // > 0 (one group: >= N)
-    const uint16_t* R; int64_t ldr;
-    const uint16_t* gate_table;
-    const uint16_t* gate_temb;
-    int64_t gate_ld;
-    int rows_per_group;
-    int tiles_m, tiles_n;
-    float* sumsq; int sumsq_cols; int64_t sumsq_ld;
 };
 
-constexpr int P2_BK = 64;
-
 template <int BM, int BN, int WAVES_M, int WAVES_N, int EPI>
-__global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_pair2_kernel(Pair2Params p) {
-    constexpr int BK = P2_BK;
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_pair2_kernel(Pair2Params pp) {
+    const GemmParams& p = pp.g;
     constexpr int NW = WAVES_M * WAVES_N;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     constexpr int MI = WM / 16, NI = WN / 16;
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_pair2_kern
     const int gn = min(GN, p.tiles_n - band * GN);
     const int tm = rem / gn, tn = band * GN + rem % gn;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int grp = n0 / p.group_cols;       // group_cols % BN == 0: a tile lies in one group
+    const int grp = n0 / pp.group_cols;       // group_cols % BN == 0: a tile lies in one group
 
     // ---- LDS-DMA sources: four descriptors (scalars) and four per-lane byte offsets.  Piece q of an operand is rows
     // 8q .. 8q+7 of the tile: the offset of piece 0 (row srow, 16-byte slot sslot ^ srow) plus q * 8 rows.
@@ -78,16 +66,16 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_pair2_kern
                                                          (int)(((int64_t)(rows_m - 1) * p.lda + p.K) * 2), 0x00020000);
     const rsrc_t d_w = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)n0 * p.ldw), 0,
                                                          (int)(((int64_t)(rows_n - 1) * p.ldw + p.K) * 2), 0x00020000);
-    const rsrc_t d_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 + (int64_t)m0 * p.lda2 + (int64_t)grp * p.K2), 0,
-                                                          (int)(((int64_t)(rows_m - 1) * p.lda2 + p.K2) * 2), 0x00020000);
-    const rsrc_t d_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W2 + (int64_t)n0 * p.ldw2), 0,
-                                                          (int)(((int64_t)(rows_n - 1) * p.ldw2 + p.K2) * 2), 0x00020000);
+    const rsrc_t d_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(pp.A2 + (int64_t)m0 * pp.lda2 + (int64_t)grp * pp.K2), 0,
+                                                          (int)(((int64_t)(rows_m - 1) * pp.lda2 + pp.K2) * 2), 0x00020000);
+    const rsrc_t d_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)(pp.W2 + (int64_t)n0 * pp.ldw2), 0,
+                                                          (int)(((int64_t)(rows_n - 1) * pp.ldw2 + pp.K2) * 2), 0x00020000);
     const uint32_t slot16 = (uint32_t)((sslot ^ srow) << 4);
     const uint32_t aoff = (uint32_t)(srow * (int)p.lda * 2) + slot16, woff = (uint32_t)(srow * (int)p.ldw * 2) + slot16;
-    const uint32_t a2off = (uint32_t)(srow * (int)p.lda2 * 2) + slot16, w2off = (uint32_t)(srow * (int)p.ldw2 * 2) + slot16;
+    const uint32_t a2off = (uint32_t)(srow * (int)pp.lda2 * 2) + slot16, w2off = (uint32_t)(srow * (int)pp.ldw2 * 2) + slot16;
     const int a_step = 16 * (int)p.lda, w_step = 16 * (int)p.ldw;                  // bytes per 8 rows
-    const int a2_step = 16 * (int)p.lda2, w2_step = 16 * (int)p.ldw2;
-    const int nk1 = p.K / BK, nk = nk1 + p.K2 / BK;                                // nk >= 2
+    const int a2_step = 16 * (int)pp.lda2, w2_step = 16 * (int)pp.ldw2;
+    const int nk1 = p.K / BK, nk = nk1 + pp.K2 / BK;                                // nk >= 2
 
     // one 1-KB LDS-DMA piece (8 rows x 128 B) of a K-tile: pieces 0..A_INSTR-1 are activation rows, the rest weight rows.
     // (ta, tw, av, wv, as, ws, kb): the pair that K-tile comes from -- descriptors, per-lane offsets, steps, byte offset in a row
@@ -196,97 +184,23 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_bf16_nt_pair2_kern
     }
 #undef LTXMI_PAIR2_PICK
 
-    // ---- epilogue: the tile kernel's sequence.  acc[i][j][e]: row m = m0 + wm*WM + i*16 + (lane&15),
-    //                                                         col n = n0 + wn*WN + j*16 + (lane>>4)*4 + e
-    // Every load is unconditional (masked lanes read a clamped address).
-    const int erow = lane & 15;
-    const int ecol = (lane >> 4) * 4;
-    constexpr bool GATED = (EPI == LTXMI_EPI_GATE_RESIDUAL);
-    constexpr bool RESID = (EPI == LTXMI_EPI_GATE_RESIDUAL || EPI == EPI_RESIDUAL);
-    u32x2 bias_v[NI], gt_v[NI];
-    int ncl[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn * WN + j * 16 + ecol;
-        ncl[j] = n < p.N ? n : p.N - 4;
-        const u32x2 b = *(const u32x2*)(p.bias + ncl[j] * p.has_bias);
-        bias_v[j] = p.has_bias ? b : u32x2{0u, 0u};
-        if (GATED) gt_v[j] = *(const u32x2*)(p.gate_table + ncl[j]);
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-        const int m = m0 + wm * WM + i * 16 + erow;
-        const bool m_ok = m < p.M;
-        const int mc = m_ok ? m : p.M - 1;
-        const uint16_t* gate_row = GATED ? p.gate_temb + (int64_t)(mc / p.rows_per_group) * p.gate_ld : nullptr;
-        float ss[NI / 4 > 0 ? NI / 4 : 1];                       // EPI_SUMSQ: one partial per 64 columns (4 fragments)
-#pragma unroll
-        for (int q = 0; q < (NI / 4 > 0 ? NI / 4 : 1); ++q) ss[q] = 0.f;
-        u32x2 ge_v[NI], rr_v[NI];
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            if (GATED) ge_v[j] = *(const u32x2*)(gate_row + ncl[j]);
-            if (RESID) rr_v[j] = *(const u32x2*)(p.R + (int64_t)mc * p.ldr + ncl[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int n = n0 + wn * WN + j * 16 + ecol;
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            add_bf16x4(v, bias_v[j]);
-            if (EPI == LTXMI_EPI_GELU_TANH) {
-                gelu_tanh_pk(v[0], v[1]);
-                gelu_tanh_pk(v[2], v[3]);
-            } else if (EPI == LTXMI_EPI_SILU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
-            }
-            if (GATED) {
-                mul_sum_bf16x4(v, gt_v[j], ge_v[j]);
-            }
-            if (RESID) {
-                add_bf16x4(v, rr_v[j]);
-            }
-            if (!(m_ok && n < p.N)) continue;
-            const u32x2 o = pack_bf16x4(v);
-            *(u32x2*)(p.C + (int64_t)m * p.ldc + n) = o;
-            if (EPI == EPI_SUMSQ)
-                ss[j / 4] = sumsq4(ss[j / 4], o);
-        }
-        if (EPI == EPI_SUMSQ) {
-            static_assert(EPI != EPI_SUMSQ || NI % 4 == 0, "sum-of-squares partials are per 64 columns");
-#pragma unroll
-            for (int q = 0; q < NI / 4; ++q) {
-                float sq = ss[q];
-                sq += __shfl_xor(sq, 16, 64);
-                sq += __shfl_xor(sq, 32, 64);
-                const int nb = n0 + wn * WN + q * 64;            // first column of this 64-column block
-                if (lane < 16 && m_ok && nb < p.sumsq_cols) p.sumsq[(int64_t)m * p.sumsq_ld + (nb >> 6)] = sq;
-            }
-        }
-    }
+    // ---- epilogue: the tile kernel's (gemm_tile.h); a missing bias is gemm.hip's zero page with stride 0, and selected to zero
+    tile_epilogue<EPI, residual_joins_bias_first(BM), /*BIAS_SELECT=*/true>(epi_args(p), acc, m0 + wm * WM, n0 + wn * WN, lane & 15, (lane >> 4) * 4);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 static int launch_pair2(const Pair2Params& p0, int epi, hipStream_t stream, const char* what) {
     Pair2Params p = p0;
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.N + BN - 1) / BN;
-    const int grid = p.tiles_m * p.tiles_n;
+    p.g.tiles_m = (p.g.M + BM - 1) / BM;
+    p.g.tiles_n = (p.g.N + BN - 1) / BN;
+    const int grid = p.g.tiles_m * p.g.tiles_n;
     constexpr int threads = WAVES_M * WAVES_N * 64;
-    constexpr int smem = 2 * (BM + BN) * P2_BK * 2;
+    constexpr int smem = 2 * (BM + BN) * BK * 2;
     auto go = [&](auto e) {
         return launch_with_lds<gemm_bf16_nt_pair2_kernel<BM, BN, WAVES_M, WAVES_N, decltype(e)::value>>(p, dim3(grid), dim3(threads),
                                                                                                  smem, stream, what);
     };
-    switch (epi) {
-        case LTXMI_EPI_NONE: return go(epi_t<LTXMI_EPI_NONE>{});
-        case EPI_SUMSQ: return go(epi_t<EPI_SUMSQ>{});
-        case LTXMI_EPI_GELU_TANH: return go(epi_t<LTXMI_EPI_GELU_TANH>{});
-        case LTXMI_EPI_SILU: return go(epi_t<LTXMI_EPI_SILU>{});
-        case LTXMI_EPI_GATE_RESIDUAL: return go(epi_t<LTXMI_EPI_GATE_RESIDUAL>{});
-        case EPI_RESIDUAL: return go(epi_t<EPI_RESIDUAL>{});
-        default: set_error("%s: bad epilogue %d", what, epi); return LTXMI_ERR_INVALID_ARG;
-    }
+    return dispatch_epilogue(epi, go, what);
 }
 
 }  // namespace ltxmi
@@ -332,26 +246,13 @@ extern "C" int ltxmi_gemm_pair2_bf16(const ltxmi_gemm_args* a, const ltxmi_gemm_
     const int kernel = pair2_plan(a, pr, "ltxmi_gemm_pair2_bf16");
     if (kernel < 0) return kernel;
     Pair2Params p = {};
-    p.A = (const uint16_t*)a->A; p.lda = a->lda;
-    p.W = (const uint16_t*)a->W; p.ldw = a->ldw;
+    int epi = 0;
+    if (const int rc = gemm_dense_params(&p.g, &epi, a, "ltxmi_gemm_pair2_bf16")) return rc;
     p.A2 = (const uint16_t*)pr->A2; p.lda2 = pr->lda2;
     p.W2 = (const uint16_t*)pr->W2; p.ldw2 = pr->ldw2;
-    p.bias = a->bias ? (const uint16_t*)a->bias : (const uint16_t*)a->W;
-    p.has_bias = a->bias ? 1 : 0;
-    p.C = (uint16_t*)a->C; p.ldc = a->ldc;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.K2 = pr->K2;
+    p.K2 = pr->K2;
     p.group_cols = pr->group_cols ? pr->group_cols : ((a->N + 255) / 256) * 256;
-    p.R = (const uint16_t*)a->residual; p.ldr = a->ldr;
-    p.gate_table = (const uint16_t*)a->gate_table;
-    p.gate_temb = (const uint16_t*)a->gate_temb;
-    p.gate_ld = a->gate_ld;
-    p.rows_per_group = a->rows_per_group > 0 ? a->rows_per_group : 1;
-    p.sumsq = a->rowsumsq;
-    p.sumsq_cols = a->rowsumsq ? a->rowsumsq_cols : 0;
-    p.sumsq_ld = a->rowsumsq ? a->rowsumsq_ld : 0;
     hipStream_t s = (hipStream_t)stream;
-    const int epi = a->rowsumsq ? EPI_SUMSQ
-                                : ((a->epilogue == LTXMI_EPI_GATE_RESIDUAL && !a->gate_table) ? EPI_RESIDUAL : a->epilogue);
     if (kernel == GEMM_PAIR2_TILE256) return launch_pair2<256, 256, 2, 4>(p, epi, s, "ltxmi_gemm_pair2_bf16");
     return launch_pair2<128, 128, 2, 2>(p, epi, s, "ltxmi_gemm_pair2_bf16");
 }

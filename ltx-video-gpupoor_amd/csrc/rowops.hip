@@ -4,31 +4,9 @@
 // (lane l takes chunks l, l+64, ...: 1 KiB coalesced per wave-instruction), reduced with
 // a 6-step wave butterfly (no LDS, no barrier), transformed in registers and written once.
 // Algorithmic traffic = one read + one write of the activation (+ the small tables).
-#include "common.h"
+#include "rows.h"
 
 namespace ltxmi {
-
-constexpr int ROWS_PER_WG = 4;  // 4 waves, one row each
-
-struct Chunk {
-    float v[8];
-};
-__device__ __forceinline__ Chunk load_chunk(const uint16_t* p) {
-    const u32x4 w = *(const u32x4*)p;
-    Chunk c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        c.v[2 * i] = bf_lo(w[i]);
-        c.v[2 * i + 1] = bf_hi(w[i]);
-    }
-    return c;
-}
-__device__ __forceinline__ void store_chunk(uint16_t* p, const Chunk& c) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf16(c.v[2 * i], c.v[2 * i + 1]);
-    *(u32x4*)p = w;
-}
 
 // ------------------------------------------------------------------ norm + AdaLN modulate
 template <int NCH, bool LAYER>
@@ -44,16 +22,12 @@ __global__ __launch_bounds__(256) void norm_modulate_kernel(
     const uint16_t* xr = x + (int64_t)row * ldx;
     Chunk c[NCH];
     float s1 = 0.f, s2 = 0.f;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        c[j] = load_bf16x8(xr + ch * 8);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            c[j] = load_chunk(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if (LAYER) s1 += c[j].v[e];
-                else s2 += c[j].v[e] * c[j].v[e];
-            }
+        for (int e = 0; e < 8; ++e) {
+            if (LAYER) s1 += c[j].v[e];
+            else s2 += c[j].v[e] * c[j].v[e];
         }
     }
     float mean = 0.f;
@@ -62,32 +36,25 @@ __global__ __launch_bounds__(256) void norm_modulate_kernel(
         // once |mean| is a few hundred standard deviations): one more butterfly, no more memory traffic
         mean = wave_sum(s1) / D;
         s2 = 0.f;
+        LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            if (lane + 64 * j < nchunk) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float d = c[j].v[e] - mean;
-                    s2 += d * d;
-                }
+            for (int e = 0; e < 8; ++e) {
+                const float d = c[j].v[e] - mean;
+                s2 += d * d;
             }
         }
     }
     const float rstd = rsqrtf(wave_sum(s2) / D + eps);
     const int64_t g = (int64_t)(row / rows_per_group) * temb_ld;
     uint16_t* yr = y + (int64_t)row * ldy;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        const Chunk a = load_bf16x8(sc_tab + ch * 8), a2 = load_bf16x8(sc_temb + g + ch * 8);
+        const Chunk b = load_bf16x8(sh_tab + ch * 8), b2 = load_bf16x8(sh_temb + g + ch * 8);
+        Chunk o;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            const Chunk a = load_chunk(sc_tab + ch * 8), a2 = load_chunk(sc_temb + g + ch * 8);
-            const Chunk b = load_chunk(sh_tab + ch * 8), b2 = load_chunk(sh_temb + g + ch * 8);
-            Chunk o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                o.v[e] = (c[j].v[e] - mean) * rstd * (1.0f + a.v[e] + a2.v[e]) + (b.v[e] + b2.v[e]);
-            store_chunk(yr + ch * 8, o);
-        }
+        for (int e = 0; e < 8; ++e)
+            o.v[e] = (c[j].v[e] - mean) * rstd * (1.0f + a.v[e] + a2.v[e]) + (b.v[e] + b2.v[e]);
+        store_bf16x8(yr + ch * 8, o);
     }
 }
 
@@ -116,38 +83,30 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(uint16_t* __restrict_
     uint16_t* xr = x + (int64_t)row * ldx;
     Chunk c[NCH];
     float s2 = 0.f;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        c[j] = load_bf16x8(xr + ch * 8);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            c[j] = load_chunk(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s2 += c[j].v[e] * c[j].v[e];
-        }
+        for (int e = 0; e < 8; ++e) s2 += c[j].v[e] * c[j].v[e];
     }
     s2 = wave_sum(s2);
     const float rstd = rsqrtf(s2 / D + eps);
     const int64_t trow = cs ? (int64_t)(row % rope_period) * ld_tab : 0;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        const Chunk wt = load_bf16x8(w + ch * 8);
+        Chunk o;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            const Chunk wt = load_chunk(w + ch * 8);
-            Chunk o;
+        for (int e = 0; e < 8; ++e) o.v[e] = c[j].v[e] * rstd * wt.v[e];
+        if (cs) {
+            const Chunk co = load_bf16x8(cs + trow + ch * 8), si = load_bf16x8(sn + trow + ch * 8);
+            Chunk r2;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o.v[e] = c[j].v[e] * rstd * wt.v[e];
-            if (cs) {
-                const Chunk co = load_chunk(cs + trow + ch * 8), si = load_chunk(sn + trow + ch * 8);
-                Chunk r2;
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    r2.v[e] = o.v[e] * co.v[e] - o.v[e + 1] * si.v[e];
-                    r2.v[e + 1] = o.v[e + 1] * co.v[e + 1] + o.v[e] * si.v[e + 1];
-                }
-                o = r2;
+            for (int e = 0; e < 8; e += 2) {
+                r2.v[e] = o.v[e] * co.v[e] - o.v[e + 1] * si.v[e];
+                r2.v[e + 1] = o.v[e + 1] * co.v[e + 1] + o.v[e] * si.v[e + 1];
             }
-            store_chunk(xr + ch * 8, o);
+            o = r2;
         }
+        store_bf16x8(xr + ch * 8, o);
     }
 }
 
@@ -166,32 +125,24 @@ __global__ __launch_bounds__(256) void pixelnorm_ada_silu_kernel(const uint16_t*
     const uint16_t* xr = x + row * C;
     Chunk c[NCH];
     float s2 = 0.f;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        c[j] = load_bf16x8(xr + ch * 8);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            c[j] = load_chunk(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s2 += c[j].v[e] * c[j].v[e];
-        }
+        for (int e = 0; e < 8; ++e) s2 += c[j].v[e] * c[j].v[e];
     }
     s2 = wave_sum(s2);
     const float rstd = rsqrtf(s2 / C + eps);
     const int64_t bofs = (row / rows_per_batch) * C;
     uint16_t* yr = y + row * C;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        Chunk o;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            Chunk o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float v = c[j].v[e] * rstd;
-                if (scale) v = v * (1.0f + scale[bofs + ch * 8 + e]) + shift[bofs + ch * 8 + e];
-                o.v[e] = apply_silu ? silu_f(v) : v;
-            }
-            store_chunk(yr + ch * 8, o);
+        for (int e = 0; e < 8; ++e) {
+            float v = c[j].v[e] * rstd;
+            if (scale) v = v * (1.0f + scale[bofs + ch * 8 + e]) + shift[bofs + ch * 8 + e];
+            o.v[e] = apply_silu ? silu_f(v) : v;
         }
+        store_bf16x8(yr + ch * 8, o);
     }
 }
 
@@ -210,7 +161,7 @@ __global__ __launch_bounds__(256) void pixelnorm_ada_silu_narrow_kernel(const ui
     const int sub = lane % LPR, rsub = lane / LPR;
     const int64_t stride = (int64_t)gridDim.x * (ROWS_PER_WG * RPW);
     for (int64_t row = ((int64_t)blockIdx.x * ROWS_PER_WG + wave) * RPW + rsub; row < rows; row += stride) {
-        Chunk c = load_chunk(x + row * C + sub * 8);
+        Chunk c = load_bf16x8(x + row * C + sub * 8);
         float s2 = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) s2 += c.v[e] * c.v[e];
@@ -232,7 +183,7 @@ __global__ __launch_bounds__(256) void pixelnorm_ada_silu_narrow_kernel(const ui
             if (scale) v = v * (1.0f + sc[e]) + sh[e];
             o.v[e] = apply_silu ? silu_f(v) : v;
         }
-        store_chunk(y + row * C + sub * 8, o);
+        store_bf16x8(y + row * C + sub * 8, o);
     }
 }
 
@@ -249,39 +200,28 @@ __global__ __launch_bounds__(256) void layernorm_affine_kernel(const uint16_t* _
     const uint16_t* xr = x + row * C;
     Chunk c[NCH];
     float s1 = 0.f;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        c[j] = load_bf16x8(xr + ch * 8);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            c[j] = load_chunk(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s1 += c[j].v[e];
-        }
+        for (int e = 0; e < 8; ++e) s1 += c[j].v[e];
     }
     const float mean = wave_sum(s1) / C;
     float s2 = 0.f;                                        // variance about the mean, as norm_modulate_kernel<LAYER>
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        if (lane + 64 * j < nchunk) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float d = c[j].v[e] - mean;
-                s2 += d * d;
-            }
+        for (int e = 0; e < 8; ++e) {
+            const float d = c[j].v[e] - mean;
+            s2 += d * d;
         }
     }
     const float rstd = rsqrtf(wave_sum(s2) / C + eps);
     uint16_t* yr = y + row * C;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        const Chunk gm = load_bf16x8(gamma + ch * 8), bt = load_bf16x8(beta + ch * 8);
+        Chunk o;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            const Chunk gm = load_chunk(gamma + ch * 8), bt = load_chunk(beta + ch * 8);
-            Chunk o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o.v[e] = (c[j].v[e] - mean) * rstd * gm.v[e] + bt.v[e];
-            store_chunk(yr + ch * 8, o);
-        }
+        for (int e = 0; e < 8; ++e) o.v[e] = (c[j].v[e] - mean) * rstd * gm.v[e] + bt.v[e];
+        store_bf16x8(yr + ch * 8, o);
     }
 }
 
@@ -306,69 +246,52 @@ __global__ __launch_bounds__(256) void qkv_norm_rope_pack_kernel(const uint16_t*
     const uint16_t* xr = x + (int64_t)row * ldx;
     Chunk cq[NCH], ck[NCH];
     float sq = 0.f, sk = 0.f;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        cq[j] = load_bf16x8(xr + ch * 8);
+        ck[j] = load_bf16x8(xr + D + ch * 8);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            cq[j] = load_chunk(xr + ch * 8);
-            ck[j] = load_chunk(xr + D + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                sq += cq[j].v[e] * cq[j].v[e];
-                sk += ck[j].v[e] * ck[j].v[e];
-            }
+        for (int e = 0; e < 8; ++e) {
+            sq += cq[j].v[e] * cq[j].v[e];
+            sk += ck[j].v[e] * ck[j].v[e];
         }
     }
     sq = wave_sum(sq);
     sk = wave_sum(sk);
     const float rq = rsqrtf(sq / D + eps), rk = rsqrtf(sk / D + eps);
     const int64_t trow = cs ? (int64_t)(row % rope_period) * ld_tab : 0;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        const int c0 = ch * 8;
+        const int p = c0 / Dp, cl = c0 - p * Dp;                        // destination rank, channel within its D / P
+        uint16_t* dst = out + ((((int64_t)p * Nl + n) * B + b) * 3) * Dp + cl;
+        const Chunk wqv = load_bf16x8(wq + c0), wkv = load_bf16x8(wk + c0);
+        Chunk oq, ok;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            const int c0 = ch * 8;
-            const int p = c0 / Dp, cl = c0 - p * Dp;                        // destination rank, channel within its D / P
-            uint16_t* dst = out + ((((int64_t)p * Nl + n) * B + b) * 3) * Dp + cl;
-            const Chunk wqv = load_chunk(wq + c0), wkv = load_chunk(wk + c0);
-            Chunk oq, ok;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                oq.v[e] = cq[j].v[e] * rq * wqv.v[e];
-                ok.v[e] = ck[j].v[e] * rk * wkv.v[e];
-            }
-            if (cs) {
-                const Chunk co = load_chunk(cs + trow + c0), si = load_chunk(sn + trow + c0);
-                Chunk r2, r3;
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    r2.v[e] = oq.v[e] * co.v[e] - oq.v[e + 1] * si.v[e];
-                    r2.v[e + 1] = oq.v[e + 1] * co.v[e + 1] + oq.v[e] * si.v[e + 1];
-                    r3.v[e] = ok.v[e] * co.v[e] - ok.v[e + 1] * si.v[e];
-                    r3.v[e + 1] = ok.v[e + 1] * co.v[e + 1] + ok.v[e] * si.v[e + 1];
-                }
-                oq = r2;
-                ok = r3;
-            }
-            store_chunk(dst, oq);
-            store_chunk(dst + Dp, ok);
-            *(u32x4*)(dst + 2 * Dp) = *(const u32x4*)(xr + 2 * D + c0);     // v: plain copy
+        for (int e = 0; e < 8; ++e) {
+            oq.v[e] = cq[j].v[e] * rq * wqv.v[e];
+            ok.v[e] = ck[j].v[e] * rk * wkv.v[e];
         }
+        if (cs) {
+            const Chunk co = load_bf16x8(cs + trow + c0), si = load_bf16x8(sn + trow + c0);
+            Chunk r2, r3;
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                r2.v[e] = oq.v[e] * co.v[e] - oq.v[e + 1] * si.v[e];
+                r2.v[e + 1] = oq.v[e + 1] * co.v[e + 1] + oq.v[e] * si.v[e + 1];
+                r3.v[e] = ok.v[e] * co.v[e] - ok.v[e + 1] * si.v[e];
+                r3.v[e + 1] = ok.v[e + 1] * co.v[e + 1] + ok.v[e] * si.v[e + 1];
+            }
+            oq = r2;
+            ok = r3;
+        }
+        store_bf16x8(dst, oq);
+        store_bf16x8(dst + Dp, ok);
+        *(u32x4*)(dst + 2 * Dp) = *(const u32x4*)(xr + 2 * D + c0);     // v: plain copy
     }
 }
-
-static inline int nch_for(int D) { return D <= 512 ? 1 : (D <= 2048 ? 4 : 16); }
 
 }  // namespace ltxmi
 
 using namespace ltxmi;
-
-#define DISPATCH_NCH(D, CALL)                  \
-    switch (nch_for(D)) {                      \
-        case 1: { constexpr int NCH = 1; CALL; } break;   \
-        case 4: { constexpr int NCH = 4; CALL; } break;   \
-        default: { constexpr int NCH = 16; CALL; } break; \
-    }
 
 extern "C" int ltxmi_norm_modulate_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int32_t D,
                                         float eps, int32_t kind, const void* scale_table, const void* scale_temb,
@@ -378,23 +301,22 @@ extern "C" int ltxmi_norm_modulate_bf16(const void* x, int64_t ldx, void* y, int
                   "ltxmi_norm_modulate_bf16: NULL argument");
     LTXMI_REQUIRE(rows > 0 && D > 0 && rows_per_group > 0, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_norm_modulate_bf16: non-positive size rows=%d D=%d", rows, D);
-    LTXMI_REQUIRE(D % 8 == 0 && D <= 8192 && ldx % 8 == 0 && ldy % 8 == 0 && temb_ld % 8 == 0, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(D) && ldx % 8 == 0 && ldy % 8 == 0 && temb_ld % 8 == 0, LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_norm_modulate_bf16: D=%d must be a multiple of 8 and <= 8192 (strides multiples of 8)", D);
     LTXMI_REQUIRE(kind == LTXMI_NORM_RMS || kind == LTXMI_NORM_LAYER, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_norm_modulate_bf16: bad kind %d", kind);
     const int grid = (rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     hipStream_t s = (hipStream_t)stream;
-#define CALLK(L)                                                                                            \
-    hipLaunchKernelGGL((norm_modulate_kernel<NCH, L>), dim3(grid), dim3(256), 0, s, (const uint16_t*)x, ldx, \
-                       (uint16_t*)y, ldy, rows, D, eps, (const uint16_t*)scale_table,                       \
-                       (const uint16_t*)scale_temb, (const uint16_t*)shift_table, (const uint16_t*)shift_temb, \
-                       temb_ld, rows_per_group)
-    if (kind == LTXMI_NORM_LAYER) {
-        DISPATCH_NCH(D, CALLK(true))
-    } else {
-        DISPATCH_NCH(D, CALLK(false))
-    }
-#undef CALLK
+    dispatch_nch<false>(D, [&](auto nch) {
+        auto go = [&](auto layer) {
+            hipLaunchKernelGGL((norm_modulate_kernel<decltype(nch)::value, decltype(layer)::value>), dim3(grid), dim3(256), 0, s,
+                               (const uint16_t*)x, ldx, (uint16_t*)y, ldy, rows, D, eps, (const uint16_t*)scale_table,
+                               (const uint16_t*)scale_temb, (const uint16_t*)shift_table, (const uint16_t*)shift_temb, temb_ld,
+                               rows_per_group);
+        };
+        if (kind == LTXMI_NORM_LAYER) go(std::true_type{});
+        else go(std::false_type{});
+    });
     return check_launch("ltxmi_norm_modulate_bf16");
 }
 
@@ -467,16 +389,17 @@ static int rmsnorm_rope_launch(void* x, int64_t ldx, int32_t rows, int32_t D, co
     LTXMI_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr), LTXMI_ERR_INVALID_ARG,
                   "ltxmi_rmsnorm_rope_bf16: cos and sin must both be given or both be NULL");
     LTXMI_REQUIRE(rows > 0 && D > 0, LTXMI_ERR_INVALID_ARG, "ltxmi_rmsnorm_rope_bf16: non-positive size");
-    LTXMI_REQUIRE(D % 8 == 0 && D <= 8192 && ldx % 8 == 0, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(D) && ldx % 8 == 0, LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_rmsnorm_rope_bf16: D=%d must be a multiple of 8 and <= 8192", D);
     if (cos_tab) LTXMI_REQUIRE(rope_period > 0 && ld_tab % 8 == 0 && ld_tab >= D, LTXMI_ERR_INVALID_ARG,
                                "ltxmi_rmsnorm_rope_bf16: bad rope table geometry");
     const int grid = (rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_NCH(D, hipLaunchKernelGGL((rmsnorm_rope_kernel<NCH>), dim3(grid), dim3(256), 0, s, (uint16_t*)x, ldx,
-                                       rows, D, (const uint16_t*)weight, eps, (const uint16_t*)cos_tab,
-                                       (const uint16_t*)sin_tab, ld_tab, rope_period > 0 ? rope_period : 1, side_ss, side_ld,
-                                       side_n, 1.0f / (float)side_d, side_eps, side_rstd))
+    dispatch_nch<false>(D, [&](auto nch) {
+        hipLaunchKernelGGL((rmsnorm_rope_kernel<decltype(nch)::value>), dim3(grid), dim3(256), 0, s, (uint16_t*)x, ldx, rows, D,
+                           (const uint16_t*)weight, eps, (const uint16_t*)cos_tab, (const uint16_t*)sin_tab, ld_tab,
+                           rope_period > 0 ? rope_period : 1, side_ss, side_ld, side_n, 1.0f / (float)side_d, side_eps, side_rstd);
+    });
     return check_launch("ltxmi_rmsnorm_rope_bf16");
 }
 
@@ -495,10 +418,11 @@ extern "C" int ltxmi_qkv_norm_rope_pack_bf16(const void* qkv, int64_t ld, int32_
                                "ltxmi_qkv_norm_rope_pack_bf16: bad rope table geometry");
     const int rows = B * Nl, grid = (rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_NCH(D, hipLaunchKernelGGL((qkv_norm_rope_pack_kernel<NCH>), dim3(grid), dim3(256), 0, s, (const uint16_t*)qkv,
-                                       ld, B, Nl, D, P, (const uint16_t*)q_weight, (const uint16_t*)k_weight, eps,
-                                       (const uint16_t*)cos_tab, (const uint16_t*)sin_tab, ld_tab,
-                                       rope_period > 0 ? rope_period : 1, (uint16_t*)out))
+    dispatch_nch<false>(D, [&](auto nch) {
+        hipLaunchKernelGGL((qkv_norm_rope_pack_kernel<decltype(nch)::value>), dim3(grid), dim3(256), 0, s, (const uint16_t*)qkv, ld, B,
+                           Nl, D, P, (const uint16_t*)q_weight, (const uint16_t*)k_weight, eps, (const uint16_t*)cos_tab,
+                           (const uint16_t*)sin_tab, ld_tab, rope_period > 0 ? rope_period : 1, (uint16_t*)out);
+    });
     return check_launch("ltxmi_qkv_norm_rope_pack_bf16");
 }
 
@@ -510,12 +434,12 @@ extern "C" int ltxmi_pixelnorm_ada_silu_bf16(const void* x, void* y, int64_t row
                   "ltxmi_pixelnorm_ada_silu_bf16: scale and shift must both be given or both be NULL");
     LTXMI_REQUIRE(rows > 0 && C > 0 && rows_per_batch > 0, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_pixelnorm_ada_silu_bf16: non-positive size");
-    LTXMI_REQUIRE(C % 8 == 0 && C <= 8192, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(C), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_pixelnorm_ada_silu_bf16: C=%d must be a multiple of 8 and <= 8192", C);
     const int64_t grid = (rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     LTXMI_REQUIRE(grid < (1ll << 31), LTXMI_ERR_UNSUPPORTED, "ltxmi_pixelnorm_ada_silu_bf16: too many rows");
     hipStream_t s = (hipStream_t)stream;
-    if ((C == 64 || C == 128 || C == 256) && ((((uintptr_t)scale | (uintptr_t)shift) & 15) == 0)) {
+    if ((C == 64 || C == 128 || C == 256) && aligned16(scale, shift)) {
         const int rpw = 512 / C;                                  // rows per wave
         int64_t g = (rows + ROWS_PER_WG * rpw - 1) / (ROWS_PER_WG * rpw);
         if (g > 256 * 16) g = 256 * 16;                           // grid-stride beyond 16 blocks per CU
@@ -528,9 +452,10 @@ extern "C" int ltxmi_pixelnorm_ada_silu_bf16(const void* x, void* y, int64_t row
 #undef CALLN
         return check_launch("ltxmi_pixelnorm_ada_silu_bf16");
     }
-    DISPATCH_NCH(C, hipLaunchKernelGGL((pixelnorm_ada_silu_kernel<NCH>), dim3((unsigned)grid), dim3(256), 0, s,
-                                       (const uint16_t*)x, (uint16_t*)y, rows, C, rows_per_batch, scale, shift,
-                                       apply_silu, eps))
+    dispatch_nch<false>(C, [&](auto nch) {
+        hipLaunchKernelGGL((pixelnorm_ada_silu_kernel<decltype(nch)::value>), dim3((unsigned)grid), dim3(256), 0, s,
+                           (const uint16_t*)x, (uint16_t*)y, rows, C, rows_per_batch, scale, shift, apply_silu, eps);
+    });
     return check_launch("ltxmi_pixelnorm_ada_silu_bf16");
 }
 
@@ -538,13 +463,14 @@ extern "C" int ltxmi_layernorm_affine_bf16(const void* x, void* y, int64_t rows,
                                            const void* beta, float eps, void* stream) {
     LTXMI_REQUIRE(x && y && gamma && beta, LTXMI_ERR_INVALID_ARG, "ltxmi_layernorm_affine_bf16: NULL argument");
     LTXMI_REQUIRE(rows > 0 && C > 0, LTXMI_ERR_INVALID_ARG, "ltxmi_layernorm_affine_bf16: non-positive size");
-    LTXMI_REQUIRE(C % 8 == 0 && C <= 8192, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(C), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_layernorm_affine_bf16: C=%d must be a multiple of 8 and <= 8192", C);
     const int64_t grid = (rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     LTXMI_REQUIRE(grid < (1ll << 31), LTXMI_ERR_UNSUPPORTED, "ltxmi_layernorm_affine_bf16: too many rows");
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_NCH(C, hipLaunchKernelGGL((layernorm_affine_kernel<NCH>), dim3((unsigned)grid), dim3(256), 0, s,
-                                       (const uint16_t*)x, (uint16_t*)y, rows, C, (const uint16_t*)gamma,
-                                       (const uint16_t*)beta, eps))
+    dispatch_nch<false>(C, [&](auto nch) {
+        hipLaunchKernelGGL((layernorm_affine_kernel<decltype(nch)::value>), dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)x,
+                           (uint16_t*)y, rows, C, (const uint16_t*)gamma, (const uint16_t*)beta, eps);
+    });
     return check_launch("ltxmi_layernorm_affine_bf16");
 }

@@ -6,49 +6,13 @@
 //   norm_modulate_f32in : one wave per row, the row held in registers between the reduction and the modulation
 //   gate_residual_f32   : no reduction -> one lane per 8-channel chunk over the flat [rows, D / 8] index, so narrow rows
 //                         share a wave
-#include "common.h"
+#include "rows.h"
 
 // What is rounded where is the specification of this path (include/ltxmi.h): every sum and product below is the single
 // correctly rounded fp32 operation it is written as, whatever -ffast-math allows elsewhere.
 #pragma clang fp reassociate(off) contract(off)
 
 namespace ltxmi {
-
-constexpr int S32_ROWS_PER_WG = 4;  // 4 waves, one row each
-
-struct Chunk8 {
-    float v[8];
-};
-__device__ __forceinline__ Chunk8 load_bf16x8(const uint16_t* p) {
-    const u32x4 w = *(const u32x4*)p;
-    Chunk8 c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        c.v[2 * i] = bf_lo(w[i]);
-        c.v[2 * i + 1] = bf_hi(w[i]);
-    }
-    return c;
-}
-__device__ __forceinline__ void store_bf16x8(uint16_t* p, const Chunk8& c) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf16(c.v[2 * i], c.v[2 * i + 1]);
-    *(u32x4*)p = w;
-}
-__device__ __forceinline__ Chunk8 load_f32x8(const float* p) {
-    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-    Chunk8 c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        c.v[i] = a[i];
-        c.v[4 + i] = b[i];
-    }
-    return c;
-}
-__device__ __forceinline__ void store_f32x8(float* p, const Chunk8& c) {
-    *(f32x4*)p = f32x4{c.v[0], c.v[1], c.v[2], c.v[3]};
-    *(f32x4*)(p + 4) = f32x4{c.v[4], c.v[5], c.v[6], c.v[7]};
-}
 
 // ------------------------------------------------- norm + AdaLN modulate, fp32 rows in, bf16 rows out
 // norm_modulate_kernel of rowops.hip with the row read as fp32: the statistics and the modulation are fp32 from the
@@ -59,22 +23,18 @@ __global__ __launch_bounds__(256) void norm_modulate_f32in_kernel(
     const uint16_t* __restrict__ sc_tab, const uint16_t* __restrict__ sc_temb, const uint16_t* __restrict__ sh_tab,
     const uint16_t* __restrict__ sh_temb, int64_t temb_ld, int rows_per_group) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * S32_ROWS_PER_WG + (threadIdx.x >> 6);
+    const int row = blockIdx.x * ROWS_PER_WG + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int nchunk = D >> 3;
     const float* xr = x + (int64_t)row * ldx;
-    Chunk8 c[NCH];
+    Chunk c[NCH];
     float s1 = 0.f, s2 = 0.f;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        c[j] = load_f32x8(xr + ch * 8);
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            c[j] = load_f32x8(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                if (LAYER) s1 += c[j].v[e];
-                else s2 += c[j].v[e] * c[j].v[e];
-            }
+        for (int e = 0; e < 8; ++e) {
+            if (LAYER) s1 += c[j].v[e];
+            else s2 += c[j].v[e] * c[j].v[e];
         }
     }
     float mean = 0.f;
@@ -82,32 +42,25 @@ __global__ __launch_bounds__(256) void norm_modulate_f32in_kernel(
         // variance about the mean from the registers, as norm_modulate_kernel<LAYER>
         mean = wave_sum(s1) / D;
         s2 = 0.f;
+        LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
 #pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            if (lane + 64 * j < nchunk) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float d = c[j].v[e] - mean;
-                    s2 += d * d;
-                }
+            for (int e = 0; e < 8; ++e) {
+                const float d = c[j].v[e] - mean;
+                s2 += d * d;
             }
         }
     }
     const float rstd = rsqrtf(wave_sum(s2) / D + eps);
     const int64_t g = (int64_t)(row / rows_per_group) * temb_ld;
     uint16_t* yr = y + (int64_t)row * ldy;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        const Chunk a = load_bf16x8(sc_tab + ch * 8), a2 = load_bf16x8(sc_temb + g + ch * 8);
+        const Chunk b = load_bf16x8(sh_tab + ch * 8), b2 = load_bf16x8(sh_temb + g + ch * 8);
+        Chunk o;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            const Chunk8 a = load_bf16x8(sc_tab + ch * 8), a2 = load_bf16x8(sc_temb + g + ch * 8);
-            const Chunk8 b = load_bf16x8(sh_tab + ch * 8), b2 = load_bf16x8(sh_temb + g + ch * 8);
-            Chunk8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                o.v[e] = (c[j].v[e] - mean) * rstd * (1.0f + (a.v[e] + a2.v[e])) + (b.v[e] + b2.v[e]);
-            store_bf16x8(yr + ch * 8, o);
-        }
+        for (int e = 0; e < 8; ++e)
+            o.v[e] = (c[j].v[e] - mean) * rstd * (1.0f + (a.v[e] + a2.v[e])) + (b.v[e] + b2.v[e]);
+        store_bf16x8(yr + ch * 8, o);
     }
 }
 
@@ -126,11 +79,11 @@ __global__ __launch_bounds__(256) void gate_residual_f32_kernel(float* __restric
     const uint32_t row = idx / (uint32_t)nchunk;
     const int c0 = (int)(idx - row * (uint32_t)nchunk) * 8;
     float* hp = h + (int64_t)row * ldh + c0;
-    Chunk8 acc = load_f32x8(hp);
-    const Chunk8 yv = load_bf16x8(y + (int64_t)row * ldy + c0);
+    Chunk acc = load_f32x8(hp);
+    const Chunk yv = load_bf16x8(y + (int64_t)row * ldy + c0);
     if (GATED) {
-        const Chunk8 gt = load_bf16x8(g_tab + c0);
-        const Chunk8 ge = load_bf16x8(g_temb + (int64_t)(row / (uint32_t)rows_per_group) * gate_ld + c0);
+        const Chunk gt = load_bf16x8(g_tab + c0);
+        const Chunk ge = load_bf16x8(g_temb + (int64_t)(row / (uint32_t)rows_per_group) * gate_ld + c0);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float gate = gt.v[e] + ge.v[e];
@@ -146,12 +99,6 @@ __global__ __launch_bounds__(256) void gate_residual_f32_kernel(float* __restric
     store_f32x8(hp, acc);
     if (COPY) store_bf16x8(hb + (int64_t)row * ldhb + c0, acc);
 }
-
-// chunks of 8 channels per lane: 1 / 4 / 8 / 16 cover D <= 512 / 2048 / 4096 / 8192 (the 13B width, 4096, keeps 64 row values
-// per lane instead of the 128 the widest instance holds)
-static inline int s32_nch_for(int D) { return D <= 512 ? 1 : (D <= 2048 ? 4 : (D <= 4096 ? 8 : 16)); }
-
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace ltxmi
 
@@ -169,34 +116,24 @@ extern "C" int ltxmi_norm_modulate_f32in_bf16(const float* x, int64_t ldx, void*
                   "ltxmi_norm_modulate_f32in_bf16: bad kind %d", kind);
     LTXMI_REQUIRE((const void*)x != (const void*)y, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_norm_modulate_f32in_bf16: y cannot alias x (fp32 rows in, bf16 rows out)");
-    LTXMI_REQUIRE(D % 8 == 0 && D <= 8192, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(D), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_norm_modulate_f32in_bf16: D=%d must be a multiple of 8 and <= 8192", D);
-    LTXMI_REQUIRE(ldx >= D && ldy >= D && ldx % 4 == 0 && ldy % 8 == 0 && temb_ld % 8 == 0 && temb_ld >= 0, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(ldx >= D && ldx % 4 == 0 && row_stride_ok(ldy, D) && temb_ld % 8 == 0 && temb_ld >= 0, LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_norm_modulate_f32in_bf16: strides must cover D=%d and keep rows 16-byte aligned (ldx %lld, ldy %lld, "
                   "temb_ld %lld)", D, (long long)ldx, (long long)ldy, (long long)temb_ld);
-    LTXMI_REQUIRE(aligned16(x) && aligned16(y) && aligned16(scale_table) && aligned16(scale_temb) && aligned16(shift_table) &&
-                      aligned16(shift_temb),
+    LTXMI_REQUIRE(aligned16(x, y, scale_table, scale_temb, shift_table, shift_temb),
                   LTXMI_ERR_UNSUPPORTED, "ltxmi_norm_modulate_f32in_bf16: every pointer must be 16-byte aligned");
-    const int grid = (rows + S32_ROWS_PER_WG - 1) / S32_ROWS_PER_WG;
+    const int grid = (rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     hipStream_t s = (hipStream_t)stream;
-#define CALLK(NCH_, L)                                                                                                 \
-    hipLaunchKernelGGL((norm_modulate_f32in_kernel<NCH_, L>), dim3(grid), dim3(256), 0, s, x, ldx, (uint16_t*)y, ldy, rows, \
-                       D, eps, (const uint16_t*)scale_table, (const uint16_t*)scale_temb, (const uint16_t*)shift_table, \
-                       (const uint16_t*)shift_temb, temb_ld, rows_per_group)
-#define CALLN(L)                         \
-    switch (s32_nch_for(D)) {            \
-        case 1: CALLK(1, L); break;      \
-        case 4: CALLK(4, L); break;      \
-        case 8: CALLK(8, L); break;      \
-        default: CALLK(16, L); break;    \
-    }
-    if (kind == LTXMI_NORM_LAYER) {
-        CALLN(true)
-    } else {
-        CALLN(false)
-    }
-#undef CALLN
-#undef CALLK
+    dispatch_nch<true>(D, [&](auto nch) {                    // (with the NCH = 8 instance: the 13B width, 4096)
+        auto go = [&](auto layer) {
+            hipLaunchKernelGGL((norm_modulate_f32in_kernel<decltype(nch)::value, decltype(layer)::value>), dim3(grid), dim3(256), 0, s,
+                               x, ldx, (uint16_t*)y, ldy, rows, D, eps, (const uint16_t*)scale_table, (const uint16_t*)scale_temb,
+                               (const uint16_t*)shift_table, (const uint16_t*)shift_temb, temb_ld, rows_per_group);
+        };
+        if (kind == LTXMI_NORM_LAYER) go(std::true_type{});
+        else go(std::false_type{});
+    });
     return check_launch("ltxmi_norm_modulate_f32in_bf16");
 }
 
@@ -214,15 +151,14 @@ extern "C" int ltxmi_gate_residual_f32(float* h, int64_t ldh, const void* y, int
                   "ltxmi_gate_residual_f32: round_product=%d must be 0 or 1", round_product);
     LTXMI_REQUIRE((const void*)h != y && (const void*)h != (const void*)h_bf16 && y != (const void*)h_bf16, LTXMI_ERR_INVALID_ARG,
                   "ltxmi_gate_residual_f32: h, y and h_bf16 are three different buffers");
-    LTXMI_REQUIRE(D % 8 == 0 && D <= 8192, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(D), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_gate_residual_f32: D=%d must be a multiple of 8 and <= 8192", D);
-    LTXMI_REQUIRE(ldh >= D && ldy >= D && ldh % 4 == 0 && ldy % 8 == 0 && (!gate_table || (gate_ld % 8 == 0 && gate_ld >= 0)) &&
-                      (!h_bf16 || (ld_h_bf16 >= D && ld_h_bf16 % 8 == 0)),
+    LTXMI_REQUIRE(ldh >= D && ldh % 4 == 0 && row_stride_ok(ldy, D) && (!gate_table || (gate_ld % 8 == 0 && gate_ld >= 0)) &&
+                      (!h_bf16 || row_stride_ok(ld_h_bf16, D)),
                   LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_gate_residual_f32: strides must cover D=%d and keep rows 16-byte aligned (ldh %lld, ldy %lld, gate_ld "
                   "%lld, ld_h_bf16 %lld)", D, (long long)ldh, (long long)ldy, (long long)gate_ld, (long long)ld_h_bf16);
-    LTXMI_REQUIRE(aligned16(h) && aligned16(y) && aligned16(gate_table) && aligned16(gate_table ? gate_temb : nullptr) &&
-                      aligned16(h_bf16),
+    LTXMI_REQUIRE(aligned16(h, y, gate_table, gate_table ? gate_temb : nullptr, h_bf16),
                   LTXMI_ERR_UNSUPPORTED, "ltxmi_gate_residual_f32: every pointer must be 16-byte aligned");
     const int nchunk = D >> 3;
     const int64_t total = (int64_t)rows * nchunk;

@@ -19,7 +19,7 @@
 //   * x = scale * s + rel[key - query] + key_bias[key] in fp32; a key at or below -1e30 (or past Lk) is -inf and gets P = 0;
 //   * the row sum is taken over the bf16-rounded P, the values the matrix pipe multiplies, and O = O^T / l is rounded once.
 // NT = ceil(Lk / 32) rounded up to a power of two is a template parameter (1, 2, 4, 8, 16): every register index is static.
-#include "common.h"
+#include "rows.h"
 
 namespace ltxmi {
 
@@ -186,30 +186,6 @@ static int launch_relbias(const RelBiasParams& p, hipStream_t stream) {
 
 // ------------------------------------------------------------------ T5LayerNorm: out of place, two roundings
 // One wave per row as rowops.hip: fp32 sum of squares in a fixed order, then y = bf16(bf16(x * rstd) * w).
-// (Chunk and its load / store are rowops.hip's, restated: they live in that file's namespace scope, not in a header, and moving them
-// would change a file whose generated code this change leaves as it is.)
-struct Chunk {
-    float v[8];
-};
-__device__ __forceinline__ Chunk load_chunk(const uint16_t* p) {
-    const u32x4 w = *(const u32x4*)p;
-    Chunk c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        c.v[2 * i] = bf_lo(w[i]);
-        c.v[2 * i + 1] = bf_hi(w[i]);
-    }
-    return c;
-}
-__device__ __forceinline__ void store_chunk(uint16_t* p, const Chunk& c) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf16(c.v[2 * i], c.v[2 * i + 1]);
-    *(u32x4*)p = w;
-}
-
-constexpr int ROWS_PER_WG = 4;
-
 // The row statistic, kept apart from the build's fast-math.  The squares are added in the order written here (reassociation
 // off): per lane its chunks in turn, eight elements each, then the wave butterfly.  The factor is 1 / sqrt(sum / D + eps) with the
 // divide, the square root and the reciprocal taken in double and rounded to fp32 after each step: a double result good to 2^-51
@@ -244,26 +220,18 @@ __global__ __launch_bounds__(256) void rmsnorm_weight_kernel(const uint16_t* __r
     const uint16_t* xr = x + (int64_t)row * ldx;
     Chunk c[NCH];
     float s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            c[j] = load_chunk(xr + ch * 8);
-            s2 = sumsq_chunk(s2, c[j].v);
-        }
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        c[j] = load_bf16x8(xr + ch * 8);
+        s2 = sumsq_chunk(s2, c[j].v);
     }
     const float rstd = rstd_rounded(wave_sum(s2), D, eps);
     uint16_t* yr = y + (int64_t)row * ldy;
+    LTXMI_FOR_ROW_CHUNKS(NCH, lane, nchunk, j, ch) {
+        const Chunk wt = load_bf16x8(w + ch * 8);
+        Chunk o;
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int ch = lane + 64 * j;
-        if (ch < nchunk) {
-            const Chunk wt = load_chunk(w + ch * 8);
-            Chunk o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o.v[e] = bf2f(f2bf(c[j].v[e] * rstd)) * wt.v[e];
-            store_chunk(yr + ch * 8, o);
-        }
+        for (int e = 0; e < 8; ++e) o.v[e] = bf2f(f2bf(c[j].v[e] * rstd)) * wt.v[e];
+        store_bf16x8(yr + ch * 8, o);
     }
 }
 
@@ -290,11 +258,11 @@ __global__ __launch_bounds__(GG_THREADS) void gated_gelu_kernel(const uint16_t* 
     for (int64_t i = (int64_t)blockIdx.x * GG_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * GG_THREADS) {
         const int64_t r = i / cpr;
         const int c = (int)(i - r * cpr) * 8;
-        const Chunk a = load_chunk(h + r * ldh + c), gt = load_chunk(h + r * ldh + F + c);
+        const Chunk a = load_bf16x8(h + r * ldh + c), gt = load_bf16x8(h + r * ldh + F + c);
         Chunk o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o.v[e] = bf2f(f2bf(gelu_tanh_full_range(a.v[e]))) * gt.v[e];
-        store_chunk(y + r * ldy + c, o);
+        store_bf16x8(y + r * ldy + c, o);
     }
 }
 
@@ -374,32 +342,28 @@ extern "C" int ltxmi_rmsnorm_weight_bf16(const void* x, int64_t ldx, void* y, in
                                          const void* weight, float eps, void* stream) {
     LTXMI_REQUIRE(x && y && weight, LTXMI_ERR_INVALID_ARG, "ltxmi_rmsnorm_weight_bf16: NULL argument");
     LTXMI_REQUIRE(rows > 0 && D > 0, LTXMI_ERR_INVALID_ARG, "ltxmi_rmsnorm_weight_bf16: non-positive size rows=%d D=%d", rows, D);
-    LTXMI_REQUIRE(D % 8 == 0 && D <= 8192 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= D && ldy >= D, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(row_width_ok(D) && row_stride_ok(ldx, D) && row_stride_ok(ldy, D), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_rmsnorm_weight_bf16: D=%d must be a multiple of 8 and <= 8192 (strides multiples of 8, >= D)", D);
-    LTXMI_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)weight) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(aligned16(x, y, weight), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_rmsnorm_weight_bf16: x, y and weight must be 16-byte aligned");
     // (a launch takes fewer than 2^32 threads: 2^24 - 1 workgroups of 256)
-    const int64_t grid = ((int64_t)rows + t5::ROWS_PER_WG - 1) / t5::ROWS_PER_WG;
+    const int64_t grid = ((int64_t)rows + ROWS_PER_WG - 1) / ROWS_PER_WG;
     LTXMI_REQUIRE(grid < (1ll << 24), LTXMI_ERR_UNSUPPORTED, "ltxmi_rmsnorm_weight_bf16: rows=%d: at most %d rows per call", rows,
-                  t5::ROWS_PER_WG * ((1 << 24) - 1));
+                  ROWS_PER_WG * ((1 << 24) - 1));
     hipStream_t s = (hipStream_t)stream;
-#define CALLN(N)                                                                                                             \
-    hipLaunchKernelGGL((t5::rmsnorm_weight_kernel<N>), dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)x, ldx, (uint16_t*)y, ldy, \
-                       rows, D, (const uint16_t*)weight, eps)
-    if (D <= 512) CALLN(1);
-    else if (D <= 2048) CALLN(4);
-    else if (D <= 4096) CALLN(8);                            // T5-XXL's d_model: the row in 64 registers, not 128
-    else CALLN(16);
-#undef CALLN
+    dispatch_nch<true>(D, [&](auto nch) {                    // (with the NCH = 8 instance: T5-XXL's d_model, 4096)
+        hipLaunchKernelGGL((t5::rmsnorm_weight_kernel<decltype(nch)::value>), dim3((unsigned)grid), dim3(256), 0, s, (const uint16_t*)x,
+                           ldx, (uint16_t*)y, ldy, rows, D, (const uint16_t*)weight, eps);
+    });
     return check_launch("ltxmi_rmsnorm_weight_bf16");
 }
 
 extern "C" int ltxmi_gated_gelu_bf16(const void* h, int64_t ldh, void* y, int64_t ldy, int32_t rows, int32_t F, void* stream) {
     LTXMI_REQUIRE(h && y, LTXMI_ERR_INVALID_ARG, "ltxmi_gated_gelu_bf16: NULL argument");
     LTXMI_REQUIRE(rows > 0 && F > 0, LTXMI_ERR_INVALID_ARG, "ltxmi_gated_gelu_bf16: non-positive size rows=%d F=%d", rows, F);
-    LTXMI_REQUIRE(F % 8 == 0 && ldh % 8 == 0 && ldy % 8 == 0 && ldh >= 2 * (int64_t)F && ldy >= F, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(F % 8 == 0 && ldh % 8 == 0 && ldh >= 2 * (int64_t)F && row_stride_ok(ldy, F), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_gated_gelu_bf16: F=%d must be a multiple of 8 (strides multiples of 8, ldh >= 2 F, ldy >= F)", F);
-    LTXMI_REQUIRE((((uintptr_t)h | (uintptr_t)y) & 15) == 0, LTXMI_ERR_UNSUPPORTED,
+    LTXMI_REQUIRE(aligned16(h, y), LTXMI_ERR_UNSUPPORTED,
                   "ltxmi_gated_gelu_bf16: h and y must be 16-byte aligned");
     const int64_t total = (int64_t)rows * (F >> 3);
     int64_t grid = (total + t5::GG_THREADS - 1) / t5::GG_THREADS;

@@ -116,7 +116,20 @@ FORM_CASES += [_case(SMALL, want=0, ldc_pad=12, c_off=4), _case(BIG, want=1, alg
 ROWSUMSQ_SHAPE = (4097, 4104, 128)       # ragged M, 17 x 17 tiles
 ROWSUMSQ_COLS = [64, 192, 320]
 
-GPU_CASES = PATH_CASES + FORM_CASES
+# The two tile kernels (ids 0 and 1) share one epilogue with the two-pair kernels: its edges on both, at shapes of a few
+# tiles.  M = 129 / 257 / 17: the last 16-row fragment partly out of range and the last tile partly empty; N = 136 (and 8):
+# N % 16 = 8, the last fragment's columns clamped on the loads and masked on the stores; K = 64 / 128 / 192: no refill, the
+# first refill, a refill into either stage.  No bias with every epilogue (a zero page with stride 0 stands in for it).
+EDGE_MN = (129, 136)
+EDGE_CASES = []
+for _want, _algo in ((0, 0), (1, 256)):
+    EDGE_CASES += [_case(EDGE_MN + (64,), epi=e, bias=False, want=_want, algo=_algo) for e in ("none", "gelu", "silu")]
+    EDGE_CASES += [_case(EDGE_MN + (128,), epi=e, bias=False, want=_want, algo=_algo) for e in ("gate", "residual")]
+    EDGE_CASES += [_case((257, 136, 192), want=_want, algo=_algo), _case((257, 136, 128), epi="gelu", want=_want, algo=_algo),
+                   _case((17, 136, 192), epi="gate", want=_want, algo=_algo), _case((17, 8, 128), want=_want, algo=_algo)]
+ROWSUMSQ_EDGE = (EDGE_MN + (64,), 64)    # (shape, rowsumsq_cols): the sums stop inside the one ragged N tile
+
+GPU_CASES = PATH_CASES + FORM_CASES + EDGE_CASES
 SLACK_MN = (200, 264)
 SLACK_CASES = sorted({(c["family"], c["epi"], c["K"]) for c in GPU_CASES} | {("plain", "none", ROWSUMSQ_SHAPE[2])})
 

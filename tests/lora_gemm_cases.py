@@ -70,6 +70,14 @@ GPU_CASES += [_case((1, 8), 64, 64, want=3)]
 # forced forms: the 256x256 kernel on the small shape, the 128x128 one on the big
 GPU_CASES += [_case(SMALL_MN, 128, 64, epi="gelu", want=4, algo=256), _case(BIG_MN, 128, 64, epi="gelu", want=3, algo=128)]
 
+# the edges of the epilogue the two forms share with gemm.hip's tile kernels (gemm_cases.EDGE_CASES), on the smallest stream
+# (K = 64 with K2 = 64: nk = 2, the pair switches inside the prologue): M = 129, N = 136, no bias with every epilogue
+for _want, _algo in ((3, 0), (4, 256)):
+    GPU_CASES += [_case(gc.EDGE_MN, 64, 64, epi=e, bias=False, want=_want, algo=_algo)
+                  for e in ("none", "gelu", "silu", "gate", "residual")]
+    GPU_CASES += [_case(gc.EDGE_MN, 64, 64, epi="gelu", want=_want, algo=_algo), _case((17, 8), 64, 128, want=_want, algo=_algo)]
+GPU_CASES += [_case((1, 8), 64, 64, want=4, algo=256)]
+
 # (family, epilogue, K of the concatenation) of every case above and of the row-sums test
 SLACK_CASES = sorted({(c["family"], c["epi"], c["K1"] + c["K2"]) for c in GPU_CASES} | {("plain", "none", 192)})
 

@@ -76,6 +76,26 @@ def test_rowsumsq_cases_name_their_kernels(cols):
         assert ops.gemm_kernel_id(rowsumsq=ss, rowsumsq_cols=cols, **kw) == want
 
 
+def test_rowsumsq_edge_case_names_its_kernels():
+    from ltxmi import ops
+    (M, N, K), cols = gc.ROWSUMSQ_EDGE
+    assert cols < N and N % 16 == 8 and M % 16 == 1
+    ss = torch.empty(M, cols // 64 + 3)
+    for bias in (True, False):
+        c = dict(M=M, N=N, K=K, epi="none", family="plain", bias=bias, algo=0)
+        for algo, want in ((0, 0), (128, 0), (256, 1)):
+            kw, _, _ = gc.call_args(dict(c, algo=algo), gc.empty_inputs(c))
+            assert ops.gemm_kernel_id(rowsumsq=ss, rowsumsq_cols=cols, **kw) == want
+
+
+def test_edge_cases_reach_both_tile_kernels():
+    for want in (0, 1):
+        mine = [c for c in gc.EDGE_CASES if c["id"] == want]
+        assert {c["epi"] for c in mine if not c["bias"]} == set(gc.EPIS)
+        assert {c["K"] for c in mine} == {64, 128, 192} and {c["M"] for c in mine} == {17, 129, 257}
+        assert {c["N"] for c in mine} == {8, 136}
+
+
 def test_truth_indexing_equals_a_naive_loop():
     """5 x 16 x 128: K-blocked gather (two blocks of 64) and rows_per_group = 2 against element-by-element loops."""
     M, N, K, P, rpg = 5, 16, 128, 2, 2

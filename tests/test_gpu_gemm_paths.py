@@ -81,6 +81,35 @@ def test_gemm_case(c):
         assert torch.equal(_run(c, d, a=d["a"]), out), "K-blocked A and contiguous A differ"
 
 
+@pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
+def test_gemm_row_sums_stop_inside_a_ragged_tile(bias):
+    """rowsumsq_cols = 64 < N = 136, M = 129, K = 64, with and without a bias, on the two tile kernels (one epilogue, shared
+    with the two-pair kernels): sums of the stored bf16 output, the output bit-equal to the call without them, nothing
+    written past the 64 columns' one block, and the same bits from both kernels."""
+    from ltxmi import ops
+    (M, N, K), cols = gc.ROWSUMSQ_EDGE
+    c = dict(M=M, N=N, K=K, epi="none", family="plain", bias=bias, algo=0)
+    d, truth, mag = _inputs(c)
+    nb = cols // 64
+    got = []
+    for algo, want in ((128, 0), (256, 1)):
+        ca = dict(c, algo=algo, id=want)
+        plain = _run(ca, d)
+        kw, out_buf, out = gc.call_args(ca, d)
+        ss = torch.full((M + 2, nb + 3), -7.0, dtype=torch.float32, device=DEV)
+        assert ops.gemm_kernel_id(rowsumsq=ss[1:M + 1], rowsumsq_cols=cols, **kw) == want
+        ops.gemm(rowsumsq=ss[1:M + 1], rowsumsq_cols=cols, **kw)
+        torch.cuda.synchronize()
+        assert gc.sentinels_intact(out_buf, out)
+        assert torch.equal(out, plain), f"algo {algo}: the output changes with rowsumsq"
+        want_ss = out[:, :cols].double().reshape(M, nb, 64).pow(2).sum(-1)
+        torch.testing.assert_close(ss[1:M + 1, :nb].double(), want_ss, rtol=1e-5, atol=1e-6)
+        assert bool((ss[:, nb:] == -7.0).all()) and bool((ss[0] == -7.0).all()) and bool((ss[M + 1] == -7.0).all())
+        got.append((out, ss))
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1]), "the two tile kernels differ"
+    _note(gc.compare(got[0][0], truth, mag, what=f"rowsumsq edge bias={bias}"), f"rowsumsq edge bias={bias}")
+
+
 @pytest.mark.parametrize("cols", gc.ROWSUMSQ_COLS)
 def test_gemm_row_sums_cut_inside_a_sub_tile(cols):
     """rowsumsq_cols a multiple of 64 but not of 256, ragged M, sentinel columns in the sums: on the three kernels the sums

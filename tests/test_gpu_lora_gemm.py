@@ -85,6 +85,32 @@ def test_the_two_forms_agree_bit_for_bit():
     assert torch.equal(_run_pair(c, d, algo=128), _run_pair(c, d, algo=256))
 
 
+@pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
+def test_row_sums_stop_inside_a_ragged_tile(bias):
+    """rowsumsq_cols = 64 < N = 136, M = 129, K = 64 + 64, with and without a bias: on both forms the output and the sums are
+    the bits of ops.gemm with the sums on the concatenation, and nothing is written past the one block of sums."""
+    from ltxmi import ops
+    (M, N, _), cols = gc.ROWSUMSQ_EDGE
+    c = lc._case((M, N), 64, 64, bias=bias)
+    d = _inputs(c)
+    ref_ss = torch.full((M, 4), -7.0, dtype=torch.float32, device=DEV)
+    ref = ops.gemm(d["a"], d["w"], d["bias"], rowsumsq=ref_ss, rowsumsq_cols=cols)
+    torch.cuda.synchronize()
+    for algo, want in ((128, 3), (256, 4)):
+        kw, out_buf, out = lc.call_args(c, d)
+        ss = torch.full((M + 2, 4), -7.0, dtype=torch.float32, device=DEV)
+        kw.update(algo=algo, rowsumsq=ss[1:M + 1], rowsumsq_cols=cols)
+        assert ops.gemm_kernel_id(**kw) == want
+        ops.gemm(**kw)
+        torch.cuda.synchronize()
+        assert gc.sentinels_intact(out_buf, out)
+        assert torch.equal(out, ref), f"algo {algo}: differs from ops.gemm on the concatenation"
+        assert torch.equal(ss[1:M + 1], ref_ss), f"algo {algo}: row sums differ"
+        assert bool((ss[:, 1:] == -7.0).all()) and bool((ss[0] == -7.0).all()) and bool((ss[M + 1] == -7.0).all())
+        want_ss = out[:, :cols].double().pow(2).sum(-1, keepdim=True)
+        torch.testing.assert_close(ss[1:M + 1, :1].double(), want_ss, rtol=1e-5, atol=1e-6)
+
+
 @pytest.mark.parametrize("cols", lc.ROWSUMSQ_COLS)
 def test_row_sums_of_squares_see_the_adapter(cols):
     """The q row sums of a packed QKV projection with an adapter: on both forms the sums and the output are the bits of the

@@ -116,3 +116,45 @@ def test_direct_convolution_kernels_do_not_spill(tmp_path):
     _pinned(usage, {"Li%dE" % e: (0, 0, 0, 2) for e in range(7)}, "conv3d_direct_v3_kernel")              # <EPI>, four waves
     _pinned(usage, {"Li4ELi128E": (0, 0, 0, 8), "Li4ELi256E": (0, 0, 0, 8), "Li8ELi256E": (0, 0, 0, 8), "Li12ELi256E": (0, 0, 0, 8),
                     "Li16ELi256E": (0, 0, 0, 8)}, "conv_split_finalize_kernel")                             # <CPT, NT>
+
+
+def _no_spill_and_occupancy(usage, pins):
+    """pins: {kernel name: {mangled template arguments ("" = not a template): waves per SIMD}}, every instance of the file:
+    none spills a VGPR or an SGPR, none has scratch, each keeps its occupancy."""
+    assert len(usage) == sum(len(v) for v in pins.values()), sorted(usage)
+    for kernel, insts in pins.items():
+        for inst, occupancy in insts.items():
+            tag = "%d%s%s" % (len(kernel), kernel, "I" + inst + "E" if inst else "")
+            name = [k for k in usage if tag in k]
+            assert len(name) == 1, (kernel, inst, sorted(usage))
+            u = usage[name[0]]
+            got = (u["VGPRs Spill"], u["SGPRs Spill"], u["ScratchSize [bytes/lane]"], u["Occupancy [waves/SIMD]"])
+            assert got == (0, 0, 0, occupancy), (name[0], got, occupancy)
+
+
+def test_row_kernels_do_not_spill_and_keep_their_occupancy(tmp_path):
+    """Every instance of rowops.hip (22), stream32.hip (14) and t5.hip (11) where the commit that introduced csrc/rows.h found it
+    (tools/codegen_diff.py --sequence against its parent: identical).  They are HBM-bound one-wave-per-row passes that hold a
+    row in registers: a spill puts the row into scratch, and occupancy is what hides their load latency.  <NCH> = 16-byte chunks
+    per lane; the NCH = 16 two-row qkv_norm_rope_pack_kernel sits at one wave per SIMD (256 VGPRs and AGPRs) by design."""
+    nch = lambda o1, o4, o16: {"Li1E": o1, "Li4E": o4, "Li16E": o16}
+    _no_spill_and_occupancy(_usage("rowops.hip", tmp_path, extra=[]), {
+        # <NCH, LAYER>
+        "norm_modulate_kernel": {"Li1ELb0E": 8, "Li1ELb1E": 8, "Li4ELb0E": 7, "Li4ELb1E": 6, "Li16ELb0E": 2, "Li16ELb1E": 2},
+        "rmsnorm_rope_kernel": nch(8, 8, 2),
+        "pixelnorm_ada_silu_kernel": nch(8, 8, 3),
+        "pixelnorm_ada_silu_narrow_kernel": {"Li8E": 8, "Li16E": 8, "Li32E": 8},                           # <lanes per row>
+        "layernorm_affine_kernel": nch(8, 8, 2),
+        "qkv_norm_rope_pack_kernel": nch(8, 4, 1),
+        "rowsumsq_rstd_kernel": {"": 8}})
+    _no_spill_and_occupancy(_usage("stream32.hip", tmp_path, extra=[]), {
+        # <NCH, LAYER>
+        "norm_modulate_f32in_kernel": {"Li1ELb0E": 8, "Li1ELb1E": 8, "Li4ELb0E": 7, "Li4ELb1E": 7, "Li8ELb0E": 4, "Li8ELb1E": 4,
+                                       "Li16ELb0E": 2, "Li16ELb1E": 2},
+        # <GATED, ROUND, COPY>
+        "gate_residual_f32_kernel": {"Lb0ELb0ELb0E": 8, "Lb0ELb0ELb1E": 8, "Lb1ELb0ELb0E": 8, "Lb1ELb0ELb1E": 8, "Lb1ELb1ELb0E": 8,
+                                     "Lb1ELb1ELb1E": 8}})
+    _no_spill_and_occupancy(_usage("t5.hip", tmp_path, extra=[]), {
+        "rmsnorm_weight_kernel": {"Li1E": 8, "Li4E": 8, "Li8E": 5, "Li16E": 2},                            # <NCH>
+        "attn_relbias_kernel": {"Li1E": 8, "Li2E": 8, "Li4E": 6, "Li8E": 4, "Li16E": 2},                   # <key steps of 32>
+        "gated_gelu_kernel": {"": 8}, "embedding_kernel": {"": 8}})

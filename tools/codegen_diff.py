@@ -8,6 +8,11 @@ Compiles gemm.hip and conv_direct.hip (plus every file named) from both csrc dir
 counts, scratch, LDS, occupancy, the instruction count and the mnemonics whose counts differ.  A kernel instance is named
 by its demangled signature.  Exit status 1 when anything differs, 0 when every instance is identical.  It is a diff tool:
 it knows no instruction and judges none.  `--json FILE` also writes the branch's table; `--markdown` prints a table for a note.
+
+`--sequence` also compares, per instance, the ORDERED list of mnemonics and reports "equal" or the position of the first
+difference: counts can match while the schedule moved.  `--from REGEX --to REGEX` adds the same comparison for the window from
+the first mnemonic matching FROM to the last matching TO (e.g. a K loop: --from s_barrier --to v_mfma); the patterns are the
+caller's, the tool compares text.  A sequence that differs counts as a difference for the exit status; a window does not.
 """
 import argparse
 import collections
@@ -42,7 +47,7 @@ def demangle(names):
 
 
 def compile_file(csrc, source, defines=()):
-    """{kernel: {"res": {field: n}, "ops": Counter(mnemonic -> n)}} of one file."""
+    """{kernel: {"res": {field: n}, "ops": Counter(mnemonic -> n), "seq": [mnemonic, ...]}} of one file."""
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "out.s")
         cmd = [HIPCC, *CXXFLAGS, *(ATTN_EXTRA if source in ATTN_FILES else []), *defines, "-S", "--cuda-device-only",
@@ -59,7 +64,7 @@ def compile_file(csrc, source, defines=()):
             m = re.search(r"remark:\s+([A-Za-z ]+(?: \[[^\]]+\])?): (\d+)", line)
             if m and name and m.group(1).strip() in dict(FIELDS):
                 res[name][m.group(1).strip()] = int(m.group(2))
-        ops, cur = {}, None
+        ops, seq, cur = {}, {}, None
         with open(asm) as f:
             for line in f:
                 m = re.match(r"^([A-Za-z_$][\w$.]*):", line)
@@ -67,6 +72,7 @@ def compile_file(csrc, source, defines=()):
                     cur = m.group(1) if m.group(1) in res else (cur if m.group(1).startswith(".L") else None)
                     if cur and cur not in ops:
                         ops[cur] = collections.Counter()
+                        seq[cur] = []
                     continue
                 if cur is None:
                     continue
@@ -77,8 +83,24 @@ def compile_file(csrc, source, defines=()):
                 if not s or s[0] in ".;/#":
                     continue
                 ops[cur][s.split()[0]] += 1
+                seq[cur].append(s.split()[0])
     names = demangle(list(res))
-    return {names[k]: {"res": res[k], "ops": ops.get(k, collections.Counter())} for k in res}
+    return {names[k]: {"res": res[k], "ops": ops.get(k, collections.Counter()), "seq": seq.get(k, [])} for k in res}
+
+
+def first_difference(p, b):
+    """"equal", or where two mnemonic lists part"""
+    if p == b:
+        return "equal (%d)" % len(b)
+    i = next((i for i, (x, y) in enumerate(zip(p, b)) if x != y), min(len(p), len(b)))
+    return "differs at %d of %d / %d: %s / %s" % (i, len(p), len(b), p[i] if i < len(p) else "(end)", b[i] if i < len(b) else "(end)")
+
+
+def window(seq, first, last):
+    """seq from the first mnemonic matching `first` to the last matching `last`, both included; [] where either is missing"""
+    lo = next((i for i, m in enumerate(seq) if re.search(first, m)), None)
+    hi = next((i for i in range(len(seq) - 1, -1, -1) if re.search(last, seq[i])), None)
+    return seq[lo:hi + 1] if lo is not None and hi is not None else []
 
 
 def short(sig):
@@ -96,7 +118,13 @@ def main():
     ap.add_argument("-D", dest="defines", action="append", default=[], help="extra -D for both trees")
     ap.add_argument("--json", help="write the branch's per-instance table here")
     ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--sequence", action="store_true", help="also compare the ordered mnemonic list of every instance")
+    ap.add_argument("--from", dest="win_from", metavar="REGEX", help="with --to: also compare this window of the sequence")
+    ap.add_argument("--to", dest="win_to", metavar="REGEX")
     a = ap.parse_args()
+    if bool(a.win_from) != bool(a.win_to) or (a.win_from and not a.sequence):
+        ap.error("--from and --to go together, with --sequence")
+    extra_cols = (["sequence"] if a.sequence else []) + (["window"] if a.win_from else [])
     a.parent_csrc, a.branch_csrc = os.path.abspath(a.parent_csrc), os.path.abspath(a.branch_csrc)
     files = list(DEFAULT_FILES) + [f for f in a.files if f not in DEFAULT_FILES]
     defines = ["-D" + d for d in a.defines]
@@ -113,8 +141,8 @@ def main():
         n_par, n_br = sum(sum(v["ops"].values()) for v in par.values()), sum(sum(v["ops"].values()) for v in br.values())
         print("== %s: %d / %d kernel instances, %d / %d instructions (parent / branch)" % (source, len(par), len(br), n_par, n_br))
         if a.markdown:
-            print("| instance | " + " | ".join(t for _, t in FIELDS) + " | instructions | differs |")
-            print("|---|" + "---|" * (len(FIELDS) + 2))
+            print("| instance | " + " | ".join(t for _, t in FIELDS) + " | instructions | differs |" + "".join(" %s |" % c for c in extra_cols))
+            print("|---|" + "---|" * (len(FIELDS) + 2 + len(extra_cols)))
         bad_here = 0
         for k in sorted(set(par) | set(br)):
             if k not in par or k not in br:
@@ -131,13 +159,22 @@ def main():
             ops = ["%s %d -> %d" % (o, p["ops"][o], b["ops"][o]) for o in sorted(set(p["ops"]) | set(b["ops"]))
                    if p["ops"][o] != b["ops"][o]]
             same = p["res"] == b["res"] and not ops
+            extra = []
+            if a.sequence:
+                extra.append(first_difference(p["seq"], b["seq"]))
+                same = same and p["seq"] == b["seq"]
+            if a.win_from:
+                extra.append(first_difference(window(p["seq"], a.win_from, a.win_to), window(b["seq"], a.win_from, a.win_to)))
             bad_here += not same
             if a.markdown:
-                print("| `%s` | %s | %s |" % (short(k), " | ".join(cols), "no" if same else ", ".join(ops) or "resources"))
+                print("| `%s` | %s | %s |%s" % (short(k), " | ".join(cols), "no" if same else ", ".join(ops) or ("resources" if p["res"] != b["res"] else "order"),
+                                                "".join(" %s |" % e for e in extra)))
             else:
                 print("  %-100s %s" % (short(k), "  ".join("%s %s" % (t, c) for (_, t), c in zip(list(FIELDS) + [("", "instr")], cols))))
                 if ops:
                     print("      mnemonic counts that differ: " + ", ".join(ops))
+                for c, e in zip(extra_cols, extra):
+                    print("      %s: %s" % (c, e))
         print("   %s" % ("identical" if not bad_here else "%d instance(s) DIFFER" % bad_here))
         differ += bad_here
     if a.json:
