@@ -28,6 +28,7 @@ from torch import nn
 
 from . import lora, ops
 from .attention_seam import pay_attention
+from .derived import DerivedOwner, cache_key
 
 BF16 = torch.bfloat16
 
@@ -103,7 +104,7 @@ class FeedForward(nn.Module):
         return out.view(*hidden_states.shape[:-1], out.shape[-1])
 
 
-class Attention(nn.Module):
+class Attention(DerivedOwner, nn.Module):
     """attention.py:368-975 (the subset LTX-Video instantiates: no group/spatial norm, no added
     KV, no LoRA).  Parameters: to_q, to_k, to_v, to_out.0, q_norm, k_norm."""
 
@@ -140,7 +141,6 @@ class Attention(nn.Module):
         self.to_k = nn.Linear(self.cross_attention_dim, self.inner_dim, bias=bias)
         self.to_v = nn.Linear(self.cross_attention_dim, self.inner_dim, bias=bias)
         self.to_out = nn.ModuleList([nn.Linear(self.inner_dim, self.out_dim, bias=out_bias), nn.Dropout(dropout)])
-        self._packs = {}
         self.set_processor(processor if processor is not None else AttnProcessor2_0())
 
     def set_processor(self, processor) -> None:                 # attention.py:575-595
@@ -149,47 +149,16 @@ class Attention(nn.Module):
     def get_processor(self, return_deprecated_lora: bool = False):
         return self.processor
 
-    # ---- packed projection weights (product-side layout; built lazily, rebuilt when a source changes)
-    def _pack(self, slot, mods):
-        """Contiguous [sum(out), in] weight (and bias) of ``mods``, cached per slot.  The key holds storage AND version
-        counter of every source tensor, so an in-place edit that autograd sees (``weight.copy_``, ``+=``, ``add_`` --
-        what a LoRA merge does) rebuilds the pack just like a reload does; the caches that derive from it (the
-        per-layer text K/V) key on the pack and follow.  NOT seen: edits through ``weight.data`` (no counter is
-        bumped) and any edit of an inference tensor (it has no counter, ``ops.tensor_version``): call
-        ``invalidate_packed()`` after those."""
-        srcs = [t for m in mods for t in (m.weight, m.bias) if t is not None]
-        key = tuple((t.data_ptr(), ops.tensor_version(t), t.dtype, t.device) for t in srcs)
-        hit = self._packs.get(slot)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                w = torch.cat([m.weight for m in mods], dim=0).contiguous()
-                b = torch.cat([m.bias for m in mods], dim=0).contiguous() if mods[0].bias is not None else None
-            hit = (key, w, b)
-            self._packs[slot] = hit
-        return hit[1], hit[2]
-
+    # ---- packed projection weights (product-side layout; built lazily, rebuilt when a source changes: ltxmi/derived.py)
     def packed_qkv(self):
         """[to_q; to_k; to_v] -> ([3D, Din], [3D]) for self-attention (one projection GEMM)."""
         if self.cross_attention_dim != self.query_dim:
             raise ValueError("ltxmi.Attention.packed_qkv: query and key/value inputs differ")
-        return self._pack("qkv", [self.to_q, self.to_k, self.to_v])
+        return self._packed_linears("qkv", [self.to_q, self.to_k, self.to_v])
 
     def packed_kv(self):
         """[to_k; to_v] -> ([2D, Dkv], [2D]) for cross-attention (the text keys / values in one GEMM)."""
-        return self._pack("kv", [self.to_k, self.to_v])
-
-    def invalidate_packed(self):
-        """Drop the packed copies (they are rebuilt on the next forward)."""
-        self._packs = {}
-        self.__dict__.pop("_text_kv_cache", None)
-
-    def _load_from_state_dict(self, *a, **k):
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **k)
+        return self._packed_linears("kv", [self.to_k, self.to_v])
 
     def forward(self, hidden_states, freqs_cis=None, encoder_hidden_states=None, attention_mask=None,
                 skip_layer_mask=None, skip_layer_strategy=None, fused_residual=None, **cross_attention_kwargs):
@@ -296,40 +265,34 @@ class AttnProcessor2_0:
                           **lora.pair(attn, "q", x2))                                      # [B*N, D]
             # The text keys/values depend on the prompt and this layer's weights only: within a generation
             # they are the same at every denoise step, so they are projected + normalised once and reused
-            # (same kernels on the same inputs: identical values).  Keyed on storage + version of the inputs;
-            # the source tensors are kept alive so an address cannot be reused while the entry exists.  An adapter on
-            # to_k / to_v changes the projection without touching a weight: the adapter epoch (bumped by attach / detach /
-            # set_lora_weights) is part of the key.
+            # (same kernels on the same inputs: identical values; the key and what it holds alive: ltxmi/derived.py).  An
+            # adapter on to_k / to_v changes the projection without touching a weight: the adapter epoch (bumped by attach /
+            # detach / set_lora_weights) is part of the key.
             ehs = encoder_hidden_states
-            key = (ehs.data_ptr(), tuple(ehs.shape), ops.tensor_version(ehs), wkv.data_ptr(), ops.tensor_version(wkv),
-                   attn.k_norm.weight.data_ptr(), ops.tensor_version(attn.k_norm.weight), lora.epoch(attn))
-            cache = attn.__dict__.setdefault("_text_kv_cache", {})
-            hit = cache.get(key) if ops.STEP_INVARIANT_CACHING else None
-            if hit is None:
-                # this forward's stacked projection (Transformer3DModel._stacked_text_kv): rows of the FULL batch's text states;
-                # a block run on the leading rows of the batch takes the leading rows
-                # or on a micro-batch of rows (sequence-parallel overlap mode) takes ITS rows: any whole-row offset into the
-                # full tensor is served; the entry lives until the end of the forward (Transformer3DModel.forward drops it)
-                ready = attn.__dict__.get("_text_kv_ready")
-                if ready is not None:
-                    full, full_version, kv_full, ready_epoch = ready
-                    row_bytes = full.stride(0) * full.element_size()
-                    off = ehs.data_ptr() - full.data_ptr()
-                    if (row_bytes > 0 and off >= 0 and off % row_bytes == 0 and ehs.shape[1:] == full.shape[1:]
-                            and off // row_bytes + Bk <= full.shape[0] and ehs.dtype == full.dtype and ehs.is_contiguous()
-                            and ops.tensor_version(full) == full_version and ready_epoch == lora.epoch(attn)):
-                        r0 = off // row_bytes
-                        hit = (kv_full[r0 * Lk:(r0 + Bk) * Lk],)
-            if hit is None:
-                e2 = ehs.reshape(Bk * Lk, -1)
-                kv = ops.gemm(e2, wkv, bkv, **lora.pair(attn, "kv", e2))           # [B*Lk, 2D]
-                ops.rmsnorm_rope_(kv[:, :D], attn.k_norm.weight, attn.k_norm.eps)
-                if len(cache) >= 4:
-                    cache.clear()
-                if ops.STEP_INVARIANT_CACHING:
-                    cache[key] = (kv, ehs, wkv)
-            else:
-                kv = hit[0]
+            kv = None
+            # this forward's stacked projection (Transformer3DModel._stacked_text_kv): rows of the FULL batch's text states;
+            # a block run on the leading rows of the batch takes the leading rows
+            # or on a micro-batch of rows (sequence-parallel overlap mode) takes ITS rows: any whole-row offset into the
+            # full tensor is served; the entry lives until the end of the forward (Transformer3DModel.forward drops it)
+            ready = attn.__dict__.get("_text_kv_ready")
+            if ready is not None:
+                full, full_key, kv_full, ready_epoch = ready
+                row_bytes = full.stride(0) * full.element_size()
+                off = ehs.data_ptr() - full.data_ptr()
+                if (row_bytes > 0 and off >= 0 and off % row_bytes == 0 and ehs.shape[1:] == full.shape[1:]
+                        and off // row_bytes + Bk <= full.shape[0] and ehs.dtype == full.dtype and ehs.is_contiguous()
+                        and cache_key((full,)) == full_key and ready_epoch == lora.epoch(attn)):
+                    r0 = off // row_bytes
+                    kv = kv_full[r0 * Lk:(r0 + Bk) * Lk]
+            if kv is None:
+                def project():
+                    e2 = ehs.reshape(Bk * Lk, -1)
+                    kv = ops.gemm(e2, wkv, bkv, **lora.pair(attn, "kv", e2))           # [B*Lk, 2D]
+                    ops.rmsnorm_rope_(kv[:, :D], attn.k_norm.weight, attn.k_norm.eps)
+                    return kv
+                # (bkv is not a source of its own: it is built with wkv and replaced with it)
+                kv = attn.derived("text_kv", 4, True).get((ehs, wkv, attn.k_norm.weight), (lora.epoch(attn),), project,
+                                                    enabled=ops.STEP_INVARIANT_CACHING)
             if fuse_q:
                 # one factor per row (a 3 us launch over 2 MB) instead of a 122 MB pass over q
                 q_fused = ((ops.rowsumsq_rstd(ss, D, attn.q_norm.eps), attn.q_norm.weight, attn.q_norm.eps), None)

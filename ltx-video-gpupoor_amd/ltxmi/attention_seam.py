@@ -13,6 +13,7 @@ in q's dtype.
 import torch
 
 from . import ops
+from .derived import DerivedCache
 
 
 def _key_bias_from_mask(attention_mask, B, Lk):
@@ -31,18 +32,12 @@ def _key_bias_from_mask(attention_mask, B, Lk):
                 "pay_attention: only key biases broadcast over queries and heads are supported "
                 f"(mask dim {d} has size {m.shape[d]} with stride {m.stride(d)})")
     # every block of a forward passes the same mask: keep its fp32 form (one conversion kernel per
-    # forward instead of one per layer); keyed on storage + version so an in-place edit invalidates it
+    # forward instead of one per layer); an in-place edit of the mask invalidates it (ltxmi/derived.py)
     # (a few entries: the micro-batches of the sequence-parallel overlap mode pass row slices of one mask in turn)
-    key = (m.data_ptr(), tuple(m.shape), tuple(m.stride()), m.dtype, ops.tensor_version(m))
-    hit = _BIAS_CACHE.get(key)
-    if hit is None:
-        if len(_BIAS_CACHE) >= 4:
-            _BIAS_CACHE.clear()
-        hit = _BIAS_CACHE[key] = (m[:, 0, 0, :].to(torch.float32).contiguous(), m)     # m kept alive: no pointer reuse
-    return hit[0]
+    return _BIAS_CACHE.get((m,), (), lambda: m[:, 0, 0, :].to(torch.float32).contiguous())
 
 
-_BIAS_CACHE = {}
+_BIAS_CACHE = DerivedCache(4)
 
 
 @torch.compiler.disable()

@@ -29,6 +29,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .derived import DerivedOwner
 from .transformer3d import _CombinedTimestepEmbeddings
 
 BF16 = torch.bfloat16
@@ -86,7 +87,7 @@ class _Conv3dParams(nn.Module):
         self.bias = nn.Parameter((torch.rand(cout) * 2 - 1) * bound)
 
 
-class CausalConv3d(nn.Module):
+class CausalConv3d(DerivedOwner, nn.Module):
     """causal_conv3d.py:7-63.  Kernel 3, stride 1 or 2 per axis; time padding by frame replication
     (2 in front when causal, 1+1 otherwise), spatial padding 1 in ``spatial_padding_mode``.
     The packed weight pads Cin up to a multiple of 64 and Cout up to a multiple of 8 with zeros
@@ -114,19 +115,15 @@ class CausalConv3d(nn.Module):
         self.pad_mode = self._PAD_MODES[spatial_padding_mode]          # what the kernel is given
         self.pad_replicate = spatial_padding_mode == "replicate"
         self.conv = _Conv3dParams(in_channels, out_channels, 3)
-        self._packed = None
 
     @property
     def weight(self):
         return self.conv.weight
 
     def packed(self, d2s=False):
-        """[Cout, 27*Cin] tap-major bf16 (+ rows re-ordered (p1 p2 p3, c') for the depth-to-space store)."""
-        # storage AND version counter of the sources: an in-place weight edit rebuilds the pack, as a reload does
-        # (edits through ``.data`` or of inference tensors bump no counter: call invalidate_packed() after those)
-        wt, bs = self.conv.weight, self.conv.bias
-        key = (wt.data_ptr(), ops.tensor_version(wt), None if bs is None else (bs.data_ptr(), ops.tensor_version(bs)), d2s)
-        if self._packed is None or self._packed[0] != key:
+        """[Cout, 27*Cin] tap-major bf16 (+ rows re-ordered (p1 p2 p3, c') for the depth-to-space store); rebuilt when the
+        weight or the bias changes (ltxmi/derived.py)."""
+        def build():
             with torch.no_grad():
                 w = self.conv.weight.permute(0, 2, 3, 4, 1)                  # [Cout, 3,3,3, Cin]
                 b = self.conv.bias
@@ -139,20 +136,8 @@ class CausalConv3d(nn.Module):
                     cp = self.out_channels // 8
                     w = w.view(cp, 8, -1).transpose(0, 1).reshape(self.out_channels, -1)
                     b = b.view(cp, 8).transpose(0, 1).reshape(-1)
-                self._packed = (key, w.contiguous().to(BF16), b.contiguous().to(BF16))
-        return self._packed[1], self._packed[2]
-
-    def invalidate_packed(self):
-        """Drop the packed copy (rebuilt on the next forward); needed after edits the key cannot see (``.data``)."""
-        self._packed = None
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._packed = None
-        return super()._load_from_state_dict(*a, **k)
+                return w.contiguous().to(BF16), b.contiguous().to(BF16)
+        return self.derived("packed").get((self.conv.weight, self.conv.bias), (d2s,), build)
 
     def forward(self, x, causal: bool = True, d2s=False, residual=None, add=None, tpad=0, out_T=0, post_norm=None,
                 keep_raw=False):

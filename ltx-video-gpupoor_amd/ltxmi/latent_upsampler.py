@@ -25,11 +25,12 @@ import torch
 from torch import nn
 
 from . import ops
+from .derived import DerivedOwner
 
 BF16 = torch.bfloat16
 
 
-class _ConvParams(nn.Module):
+class _ConvParams(DerivedOwner, nn.Module):
     """nn.Conv2d / nn.Conv3d(kernel 3, padding 1) parameters under the reference's names."""
 
     def __init__(self, cin, cout, dims):
@@ -38,13 +39,12 @@ class _ConvParams(nn.Module):
         bound = 1.0 / math.sqrt(cin * 3 ** dims)
         self.weight = nn.Parameter((torch.rand(cout, cin, *([3] * dims)) * 2 - 1) * bound)
         self.bias = nn.Parameter((torch.rand(cout) * 2 - 1) * bound)
-        self._packed = None
 
     def packed(self, shuffle=0):
         """(weight [cout, taps * cin] tap-major, bias) in bf16.  shuffle = n in {1, 2, 3}: the rows feed PixelShuffleND(n),
-        whose channel split is (c p1 .. pn); they are reordered to (p1 .. pn c) so that the shuffle moves whole runs of c."""
-        key = (self.weight.data_ptr(), shuffle)
-        if self._packed is None or self._packed[0] != key:
+        whose channel split is (c p1 .. pn); they are reordered to (p1 .. pn c) so that the shuffle moves whole runs of c.
+        Rebuilt when the weight or the bias changes (ltxmi/derived.py)."""
+        def build():
             with torch.no_grad():
                 cout = self.weight.shape[0]
                 perm = (0, 2, 3, 1) if self.dims == 2 else (0, 2, 3, 4, 1)
@@ -55,16 +55,8 @@ class _ConvParams(nn.Module):
                     c = cout // f
                     w = w.view(c, f, -1).transpose(0, 1).reshape(cout, -1)
                     b = b.view(c, f).transpose(0, 1).reshape(-1)
-                self._packed = (key, w.contiguous().to(BF16), b.contiguous().to(BF16))
-        return self._packed[1], self._packed[2]
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._packed = None
-        return super()._load_from_state_dict(*a, **k)
+                return w.contiguous().to(BF16), b.contiguous().to(BF16)
+        return self.derived("packed").get((self.weight, self.bias), (shuffle,), build)
 
     def forward(self, x, shuffle=0):
         """x NDHWC bf16."""

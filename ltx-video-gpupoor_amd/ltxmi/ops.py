@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, derived
 from ._lib import lib, check
 
 BF16 = torch.bfloat16
@@ -92,15 +92,10 @@ def _rows(t):
     return t2, t2.shape[0], t2.stride(0)
 
 
-def tensor_version(t):
-    """``t._version`` for the cache keys of packed weights and derived caches.  Inference tensors (weights created,
-    loaded or cast under ``torch.inference_mode()``) track no version counter and raise on the read: the key then rests
-    on storage, dtype and device alone (-1 here).  Edits made through ``.data`` bump no counter either: after those
-    call ``invalidate_packed()`` on the module (``Attention`` / ``CausalConv3d``)."""
-    try:
-        return t._version
-    except RuntimeError:
-        return -1
+# alias kept for tools: the cache keys of packed weights and derived tensors live in ltxmi/derived.py, whose docstring says
+# what they cannot see and when to call ``invalidate_packed()`` (``Attention``, ``CausalConv3d``, the upsampler's
+# ``_ConvParams``, the T5 attention / feed-forward modules, ``T5EncoderModel``, ``Transformer3DModel``)
+tensor_version = derived.tensor_version
 
 
 def _chk_bf16_any_device(*ts):

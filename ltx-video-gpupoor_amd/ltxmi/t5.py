@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .derived import DerivedOwner
 
 MAX_TOKENS = 512                     # ltxmi_attention_relbias_bf16: a query's score row is held in registers
 
@@ -95,19 +96,12 @@ class T5LayerNorm(nn.Module):
         return ops.rmsnorm_weight(x, self.weight, self.variance_epsilon, out=out)
 
 
-class _Packs:
-    """Stacked GEMM operands ([q; k; v], [wi_0; wi_1]) built on first use and cached against the source parameters'
-    storage and version counters, as Attention._pack does for the DiT."""
+class _Packs(DerivedOwner):
+    """Stacked GEMM operands ([q; k; v], [wi_0; wi_1]) built on first use and cached against their source parameters
+    (ltxmi/derived.py), as the DiT's Attention does."""
 
     def _pack(self, slot, mods):
-        srcs = [m.weight for m in mods]
-        key = tuple((t.data_ptr(), ops.tensor_version(t), t.dtype, t.device) for t in srcs)
-        hit = self.__dict__.setdefault("_packs", {}).get(slot)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, torch.cat([t.detach() for t in srcs], 0).contiguous())
-            self._packs[slot] = hit
-        return hit[1]
+        return self._packed_linears(slot, mods)[0]
 
     def _share_packed(self, slot, mods):
         """For a frozen encoder (``loading.load_t5_encoder``): build the stacked operand once and re-point the members'
@@ -120,19 +114,7 @@ class _Packs:
             n = m.weight.shape[0]
             m.weight = nn.Parameter(packed[row:row + n], requires_grad=False)
             row += n
-        key = tuple((m.weight.data_ptr(), ops.tensor_version(m.weight), m.weight.dtype, m.weight.device) for m in mods)
-        self.__dict__.setdefault("_packs", {})[slot] = (key, packed)
-
-    def invalidate_packed(self):
-        self.__dict__["_packs"] = {}
-
-    def _load_from_state_dict(self, *a, **k):
-        self.invalidate_packed()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate_packed()
-        return super()._apply(fn, *a, **k)
+        self.derived(slot).put([t for m in mods for t in (m.weight, m.bias)], (), (packed, None))
 
 
 class T5Attention(_Packs, nn.Module):
@@ -219,7 +201,7 @@ _REFUSED = {
 }
 
 
-class T5EncoderModel(nn.Module):
+class T5EncoderModel(DerivedOwner, nn.Module):
     """``transformers.T5EncoderModel`` for inference on the GPU, with the HF call protocol ``encode_prompt`` uses:
     ``model(input_ids, attention_mask=mask)[0]`` is the last hidden state [B, L, d_model] in bf16."""
 
@@ -228,7 +210,6 @@ class T5EncoderModel(nn.Module):
         self.config = cfg = config if isinstance(config, T5Config) and not kw else T5Config(config, **kw)
         self.shared = nn.Embedding(cfg.vocab_size, cfg.d_model)
         self.encoder = T5Stack(cfg)
-        self._rel_cache = {}
 
     @property
     def dtype(self):
@@ -244,21 +225,14 @@ class T5EncoderModel(nn.Module):
         alias = sd.pop("encoder.embed_tokens.weight", None)
         if alias is not None:
             sd.setdefault("shared.weight", alias)
-        self._rel_cache = {}
         return super().load_state_dict(sd, strict=strict, **kw)
-
-    def _apply(self, fn, *a, **k):
-        self._rel_cache = {}
-        return super()._apply(fn, *a, **k)
 
     def rel_bias(self, L):
         """Block 0's bias table expanded over the offsets of an L x L call, once per (L, weight version); every block reads it."""
         w = self.encoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
-        key = (L, w.data_ptr(), ops.tensor_version(w), w.dtype, w.device)
-        if self._rel_cache.get("key") != key:
-            self._rel_cache = {"key": key, "rel": build_rel_bias(w, L, L, self.config.relative_attention_num_buckets,
-                                                                 self.config.relative_attention_max_distance)}
-        return self._rel_cache["rel"]
+        cfg = self.config
+        return self.derived("rel_bias").get((w,), (L,), lambda: build_rel_bias(
+            w, L, L, cfg.relative_attention_num_buckets, cfg.relative_attention_max_distance))
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, return_dict=None, **kwargs):

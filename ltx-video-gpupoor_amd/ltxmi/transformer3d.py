@@ -19,6 +19,7 @@ from torch import nn
 
 from . import lora, ops
 from .attention import BasicTransformerBlock, SkipLayerStrategy
+from .derived import DerivedOwner, cache_key
 
 BF16 = torch.bfloat16
 
@@ -77,7 +78,7 @@ class _Config(dict):
     __getattr__ = dict.__getitem__
 
 
-class Transformer3DModel(nn.Module):
+class Transformer3DModel(DerivedOwner, nn.Module):
     def __init__(self, num_attention_heads: int = 16, attention_head_dim: int = 88,
                  in_channels: Optional[int] = None, out_channels: Optional[int] = None, num_layers: int = 1,
                  dropout: float = 0.0, norm_num_groups: int = 32, cross_attention_dim: Optional[int] = None,
@@ -261,21 +262,18 @@ class Transformer3DModel(nn.Module):
         packs = [b.attn2.packed_kv() for b in blocks]
         if any(bk is None for _, bk in packs) or len({tuple(w.shape) for w, _ in packs}) != 1:
             return
-        key = tuple((w.data_ptr(), ops.tensor_version(w), bk.data_ptr(), ops.tensor_version(bk)) for w, bk in packs)
-        st = self.__dict__.get("_stacked_kv_weights")
-        if st is None or st[0] != key:
+
+        def stack():
             with torch.no_grad():
-                st = (key, torch.cat([w for w, _ in packs], 0).contiguous(), torch.cat([bk for _, bk in packs], 0).contiguous(),
-                      packs)                                                        # (packs kept alive: no address reuse)
-            self.__dict__["_stacked_kv_weights"] = st
-        _, w_all, b_all, _ = st
+                return torch.cat([w for w, _ in packs], 0).contiguous(), torch.cat([bk for _, bk in packs], 0).contiguous()
+        w_all, b_all = self.derived("stacked_kv").get([t for pack in packs for t in pack], (), stack)
         Bk, Lk, _ = ehs.shape
         two_d = packs[0][0].shape[0]
         kv_all = ops.gemm(ehs.reshape(Bk * Lk, -1), w_all, b_all)                       # [B T, L 2D]
         for i, b in enumerate(blocks):
             kv = kv_all[:, i * two_d:(i + 1) * two_d]
             ops.rmsnorm_rope_(kv[:, :two_d // 2], b.attn2.k_norm.weight, b.attn2.k_norm.eps)
-            b.attn2.__dict__["_text_kv_ready"] = (ehs, ops.tensor_version(ehs), kv, lora.epoch(b.attn2))
+            b.attn2.__dict__["_text_kv_ready"] = (ehs, cache_key((ehs,)), kv, lora.epoch(b.attn2))
 
     def _run_blocks_microbatched(self, hidden_states, slices, freqs_cis, attention_mask, encoder_hidden_states,
                                  encoder_attention_mask, temb, cross_attention_kwargs, class_labels, layer_mask,
@@ -384,20 +382,12 @@ class Transformer3DModel(nn.Module):
         # 2. text projection
         if self.caption_projection is not None:
             # the prompt does not change between the denoise steps of a generation: project it once per
-            # (prompt tensor, weights) and hand the SAME tensor to the blocks, whose text K/V caches key on it
+            # (prompt tensor, weights and biases) and hand the SAME tensor to the blocks, whose text K/V caches key on it
             ehs = encoder_hidden_states
             cp = self.caption_projection
-            key = (ehs.data_ptr(), tuple(ehs.shape), ehs.dtype, ops.tensor_version(ehs), cp.linear_1.weight.data_ptr(),
-                   ops.tensor_version(cp.linear_1.weight), cp.linear_2.weight.data_ptr(), ops.tensor_version(cp.linear_2.weight))
-            cache = self.__dict__.setdefault("_caption_cache", {})
-            hit = cache.get(key) if ops.STEP_INVARIANT_CACHING else None
-            if hit is None:
-                if len(cache) >= 4:
-                    cache.clear()
-                hit = (cp(ehs.to(dtype)).view(B, -1, D), ehs)                    # ehs kept alive: no address reuse
-                if ops.STEP_INVARIANT_CACHING:
-                    cache[key] = hit
-            encoder_hidden_states = hit[0]
+            encoder_hidden_states = self.derived("caption", 4, True).get(
+                (ehs, cp.linear_1.weight, cp.linear_1.bias, cp.linear_2.weight, cp.linear_2.bias), (),
+                lambda: cp(ehs.to(dtype)).view(B, -1, D), enabled=ops.STEP_INVARIANT_CACHING)
 
         if joint_pass and ops.STACKED_TEXT_KV and not ops.STEP_INVARIANT_CACHING and encoder_hidden_states is not None:
             self._stacked_text_kv(encoder_hidden_states)

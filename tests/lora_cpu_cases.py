@@ -205,7 +205,7 @@ def case_caches():
     # without step-invariant caching a joint pass uses the stacked projection: not with an adapter on a to_k / to_v
     ops.set_step_invariant_caching(False)
     try:
-        m.__dict__.pop("_stacked_kv_weights", None)
+        m.derived("stacked_kv").clear()
         base2 = forward()
         assert torch.equal(base2, base)
         m.attach_lora(kv, name="kv")

@@ -172,7 +172,7 @@ def test_transformer_stacked_text_kv_is_bit_identical(alias):
         ref = m(x.to(DEV), encoder_hidden_states=encd, **kw)[0]
         ops.STACKED_TEXT_KV = True
         out = m(x.to(DEV), encoder_hidden_states=encd, **kw)[0]
-        assert "_stacked_kv_weights" in m.__dict__                          # the stacked path ran ...
+        assert "stacked_kv" in m.derived_slots()                          # the stacked path ran ...
         assert all("_text_kv_ready" not in b.attn2.__dict__ for b in m.transformer_blocks)   # ... and every block took its slice
         assert torch.equal(out, ref)
         # another prompt tensor: new projection, not the previous forward's
@@ -1284,7 +1284,7 @@ def test_microbatched_block_loop_as_the_first_forward_of_a_fresh_model():
         return out
 
     fresh = build_model(cfg, sd32)
-    assert all(not b.attn1._packs and not b.attn2._packs for b in fresh.transformer_blocks)
+    assert all(not b.attn1.derived_slots() and not b.attn2.derived_slots() for b in fresh.transformer_blocks)
     first = run(fresh, _microbatches=slices)                               # nothing was ever packed before this call
     plain = run(build_model(cfg, sd32))
     assert torch.equal(first, plain)

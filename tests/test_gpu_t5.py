@@ -59,9 +59,10 @@ def test_encoder_against_float64_with_the_cpu_bf16_run_as_yardstick(case):
     assert torch.equal(model(ids.to(DEV), attention_mask=mask.to(DEV))[0], got)
     # the bias with the sign of (key - query) flipped: operand[h, centre + d] <-> operand[h, centre - d]
     rel, center = model.rel_bias(L)
-    model._rel_cache["rel"] = (rel.flip(-1).contiguous(), center)
+    table = model.encoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
+    model.derived("rel_bias").put((table,), (L,), (rel.flip(-1).contiguous(), center))
     bad = model(ids.to(DEV), attention_mask=mask.to(DEV))[0]
-    model._rel_cache = {}
+    model.invalidate_packed()
     bad_max, bad_rms = td.errors(bad, truth)
     print(f"t5 {name}: flipped bias max abs {bad_max:.4g}, rms {bad_rms:.4g}")
     assert bad_max > 2.0 * cpu_max and bad_rms > 2.0 * cpu_rms

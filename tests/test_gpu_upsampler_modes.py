@@ -164,3 +164,26 @@ def test_upsample_latents_with_a_temporal_upsampler():
     b, c, f, h, w = shape
     assert got.dtype == torch.float32 and tuple(got.shape) == tuple(truth.shape) == (b, c, 2 * f - 1, h, w)
     assert_parity(got, truth, eager, "upsample_latents, temporal upsampler")
+
+
+def test_in_place_weight_edit_rebuilds_the_packed_conv_weight():
+    """``weight.mul_(0.5)`` on a ResBlock convolution between two runs: the second run is, bit for bit, that of a fresh model
+    loaded from the edited state dict (the pack keys on the weight's version counter, ltxmi/derived.py), not the first run again."""
+    import ltxmi
+    from oracle import upsampler as ou
+    cfg = dict(MODES["spatial_temporal"], num_blocks_per_stage=1)
+    sd = {k: v.to(BF).float() for k, v in ou.init_state_dict(cfg, seed=6).items()}
+
+    def load(state):
+        m = ltxmi.LatentUpsampler.from_config(cfg)
+        m.load_state_dict(state, strict=True)
+        return m.to(device=DEV, dtype=BF).eval()
+    z = torch.randn(1, 128, 3, 4, 4, generator=torch.Generator().manual_seed(16)).to(BF).to(DEV)
+    m = load(sd)
+    with torch.no_grad():
+        first = m(z)
+        m.res_blocks[0].conv1.weight.mul_(0.5)
+        second = m(z)
+        fresh = load({k: v.float().cpu() for k, v in m.state_dict().items()})(z)
+    assert torch.equal(second, fresh)
+    assert not torch.equal(second, first)

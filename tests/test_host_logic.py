@@ -132,13 +132,13 @@ with torch.no_grad():
     for alias in (0, 2):
         ops.STACKED_TEXT_KV = False
         ref = m(x.clone(), stg_alias_blocks=alias, **kw)[0]
-        assert "_stacked_kv_weights" not in m.__dict__
+        assert "stacked_kv" not in m.derived_slots()
         ops.STACKED_TEXT_KV = True
         out = m(x.clone(), stg_alias_blocks=alias, **kw)[0]
         assert torch.equal(out, ref), alias
-        assert "_stacked_kv_weights" in m.__dict__
+        assert "stacked_kv" in m.derived_slots()
         assert all("_text_kv_ready" not in b.attn2.__dict__ for b in m.transformer_blocks)
-        del m.__dict__["_stacked_kv_weights"]
+        m.derived("stacked_kv").clear()
     # a block that sees OTHER rows than the leading ones must not take the hand-over
     m._stacked_text_kv(m.caption_projection(enc).view(B, T, -1))
     blk = m.transformer_blocks[0]
@@ -148,9 +148,9 @@ with torch.no_grad():
     # with the cache on nothing is stacked
     ops.set_step_invariant_caching(True)
     for b in m.transformer_blocks: b.attn2.__dict__.pop("_text_kv_ready", None)
-    m.__dict__.pop("_stacked_kv_weights", None)
+    m.derived("stacked_kv").clear()
     m(x.clone(), **kw)
-    assert "_stacked_kv_weights" not in m.__dict__
+    assert "stacked_kv" not in m.derived_slots()
 print("ok")
 """
     r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=600)

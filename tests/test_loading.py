@@ -92,7 +92,7 @@ def test_packed_weights_follow_in_place_edits():
     from ltxmi.autoencoder import CausalConv3d
     att = Attention(query_dim=128, heads=2, dim_head=64, bias=True, qk_norm="rms_norm")
     w1, b1 = att.packed_qkv()
-    assert w1.shape == (384, 128) and torch.equal(w1[:128], att.to_q.weight) and set(att._packs) == {"qkv"}
+    assert w1.shape == (384, 128) and torch.equal(w1[:128], att.to_q.weight) and att.derived_slots() == {"qkv"}
     assert att.packed_qkv()[0] is w1                                  # cached while nothing changes
     with torch.no_grad():
         att.to_k.weight.add_(1.0)                                     # in place: same storage, new version
@@ -103,7 +103,7 @@ def test_packed_weights_follow_in_place_edits():
     assert torch.equal(att.packed_qkv()[1][256:], att.to_v.bias)
     cross = Attention(query_dim=128, cross_attention_dim=128, heads=2, dim_head=64, bias=True, qk_norm="rms_norm")
     wkv, _ = cross.packed_kv()
-    assert wkv.shape == (256, 128) and set(cross._packs) == {"kv"}
+    assert wkv.shape == (256, 128) and cross.derived_slots() == {"kv"}
     conv = CausalConv3d(64, 64)
     p1, _ = conv.packed()
     with torch.no_grad():
@@ -111,7 +111,7 @@ def test_packed_weights_follow_in_place_edits():
     p2, _ = conv.packed()
     assert p2 is not p1 and torch.allclose(p2.float(), p1.float() * 0.5, atol=1e-2)
     # what the key can NOT see: an edit through .data bumps no version counter -> the pack is stale until
-    # invalidate_packed() (documented on Attention._pack / CausalConv3d.packed)
+    # invalidate_packed() (documented in ltxmi/derived.py)
     v0 = att.to_q.weight._version
     att.to_q.weight.data.add_(1.0)
     assert att.to_q.weight._version == v0
