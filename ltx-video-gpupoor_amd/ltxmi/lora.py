@@ -12,7 +12,11 @@ take packed adapters: ``down = [down_q; down_k; down_v]``, one ``T [M, 3R]``, ``
 columns [g R, (g + 1) R) of T (``a2_group_cols = D``); a member without an adapter contributes zero blocks.
 
 State per linear (``LoraSlot``) is rebuilt on attach / detach / weight change, cost O(adapter); with no adapter attached no
-slot exists and every call the package makes is the one it makes without this module."""
+slot exists and every call the package makes is the one it makes without this module.
+
+The other way to run an adapter, for strengths that stay fixed over a generation, is to FUSE it into the weights
+(``Transformer3DModel.fuse_lora``; the second half of this file): one launch of the GEMM per linear, exact and reversible, after
+which the model runs the kernels of a model without adapters."""
 from collections import OrderedDict
 
 import torch
@@ -174,3 +178,168 @@ def rebuild(model):
             for owner, slots in owners.values():
                 owner.__dict__["_lora"] = slots or None
                 owner.__dict__["_lora_epoch"] = ep
+
+
+# ---------------------------------------------------------------------------------------------------- adapters fused into the weights
+# ``fuse_lora`` folds an adapter into the weight of every linear it names: W' = bf16(fp32(W + sum_r bf16(s up)[n, r] down[r, k])),
+# ONE launch of the GEMM per linear with the base weight as the residual, one rounding for all fused adapters of the linear
+# together.  A fused model carries no LoraSlot: every ``pair`` above returns {} and the forward is the one of a model without
+# adapters.  The record (``FusedState``) lives in the model's ``__dict__`` under ``_lora_fused``; ``refuse``, ``rebuild``,
+# ``epoch`` and ``_lora_adapters`` neither see it nor change.  Staleness: derived.py keys the packs and the text K/V caches on
+# address + version counter, and the GEMM writes through a raw pointer, so ``_touch`` moves the counter after every merge.
+
+class FusedState:
+    """adapters: {name: [adapter, weight, [paths]]} in insertion order; base: {path: bf16 copy of the weight before any merge}
+    for the linears with a fused adapter (and only those); sealed: paths of the linears merged with ``keep_base=False``, whose
+    base is gone."""
+    __slots__ = ("adapters", "base", "sealed")
+
+    def __init__(self):
+        self.adapters, self.base, self.sealed = OrderedDict(), {}, set()
+
+
+class _Weight:                         # what ``_member_state`` reads of a linear
+    __slots__ = ("weight",)
+
+    def __init__(self, weight):
+        self.weight = weight
+
+
+def fused_state(model, create=False):
+    st = model.__dict__.get("_lora_fused")
+    if st is None and create:
+        st = model.__dict__["_lora_fused"] = FusedState()
+    return st
+
+
+def merged_weight(base, entries, out=None, what="the linear"):
+    """bf16(fp32(base + sum over ``entries`` = [(down [r, K], up [N, r], s)] of bf16(s up) @ down)) for a bf16 ``base`` [N, K]:
+    the fp32 sum includes the base and is rounded once.  The operands are ``_member_state``'s, so a fused and an unmerged
+    adapter see the same bf16 values; r is padded with exact zeros to what the GEMM's entry check takes (and K, where it is no
+    multiple of 8, in a widened copy).  ``out`` may be ``base`` itself (the residual epilogue reads an element before it writes
+    it).  A leading dimension or an address the GEMM refuses raises, naming ``what``."""
+    if base.dim() != 2 or base.dtype != BF16 or base.stride(1) != 1:
+        raise TypeError(f"ltxmi.lora: '{what}': a merge needs a 2-D bfloat16 weight, got {base.dtype} {tuple(base.shape)}")
+    n_out, k_in = base.shape
+    for down, up, _ in entries:
+        if down.dim() != 2 or up.dim() != 2 or down.shape[1] != k_in or up.shape[0] != n_out or up.shape[1] != down.shape[0]:
+            raise ValueError(f"ltxmi.lora: '{what}' is [{up.shape[0]}, r] x [r, {down.shape[1]}] but the linear is {(n_out, k_in)}")
+    if out is None:
+        out = torch.empty((n_out, k_in), dtype=BF16, device=base.device)
+    elif out.shape != base.shape or out.dtype != BF16 or out.device != base.device:
+        raise ValueError(f"ltxmi.lora: '{what}': out must be a bfloat16 {(n_out, k_in)} tensor on {base.device}")
+    with torch.no_grad():
+        down_cat, up_cat = _member_state(_Weight(base), entries)
+        if k_in % 8:
+            # the GEMM's N is a multiple of 8: merge a copy widened by zero columns, keep the first K (exact zeros change no bit)
+            k8 = (k_in + 7) // 8 * 8
+            wide = merged_weight(_pad_to(base, cols=k8), [(_pad_to(down_cat, cols=k8), up_cat, 1.0)], what=what)
+            out.copy_(wide[:, :k_in])
+            return out
+        R = (down_cat.shape[0] + RANK_PAD - 1) // RANK_PAD * RANK_PAD
+        while True:
+            a = _pad_to(up_cat, cols=R)                                   # [N, R]
+            w = _pad_to(down_cat, rows=R).t().contiguous()                # [K, R]
+            kernel = ops.gemm_kernel_id(a, w, None, out, ops.EPI_GATE_RESIDUAL, base)
+            if kernel >= 0 or R >= 2 * RANK_PAD:
+                break
+            R += RANK_PAD                                                 # a shape refused for a small K: zeros change no bit
+        if kernel < 0:
+            raise ValueError(f"ltxmi.lora: '{what}' {(n_out, k_in)} (leading dimensions {base.stride(0)}, {out.stride(0)}) cannot "
+                             f"be merged: the GEMM refuses it ({kernel}): {ops.lib.ltxmi_last_error().decode()}")
+        # no gate table: the kernel's EPI_RESIDUAL, acc + bias + residual in fp32 and one pack_bf16
+        ops.gemm(a, w, None, out=out, epilogue=ops.EPI_GATE_RESIDUAL, residual=base)
+    return out
+
+
+def _touch(model, path, weight):
+    """The merge wrote ``weight`` through a raw pointer: move its version counter (an in-place op on an empty view of it -- no
+    element is written, the parameter and its storage stay).  An inference tensor has no counter: drop what was derived."""
+    from .derived import tensor_version
+    if tensor_version(weight) >= 0:
+        with torch.no_grad():
+            weight.narrow(0, 0, 0).zero_()
+    else:
+        owner = model
+        model.invalidate_packed()
+        for p in path.split(".")[:-1]:
+            owner = owner[int(p)] if p.isdigit() else getattr(owner, p)
+            if hasattr(owner, "invalidate_packed"):
+                owner.invalidate_packed()
+
+
+def fuse_paths(model, adapter):
+    """The module paths of ``adapter``, all 17 kinds; raises as ``attach_lora`` does on a path that names no linear of this
+    model and on a shape that does not fit."""
+    mine, other = split_targets(adapter, len(model.transformer_blocks))
+    check_shapes(model, adapter, mine)
+    for path in other:
+        try:
+            lin = _get(model, path)
+        except AttributeError:
+            lin = None
+        if lin is None:
+            raise KeyError(f"ltxmi.lora: '{path}' names no linear of this model")
+        down, up, _ = adapter.modules[path]
+        if down.shape[1] != lin.weight.shape[1] or up.shape[0] != lin.weight.shape[0]:
+            raise ValueError(f"ltxmi.lora: '{path}' is [{up.shape[0]}, r] x [r, {down.shape[1]}] but the linear is "
+                             f"{tuple(lin.weight.shape)}")
+    return list(mine.values()) + other
+
+
+def check_mergeable(model, paths):
+    """Raise, naming the linear, where ``merged_weight`` would: asked of the GEMM's entry check for every weight of ``paths``
+    before the first one is written (no launch; the operands stand in by shape, the weight by its own address and stride)."""
+    stand_in = {}
+    for path in paths:
+        w = _get(model, path).weight
+        if w.dim() != 2 or w.dtype != BF16 or w.stride(1) != 1:
+            raise TypeError(f"ltxmi.lora: '{path}': a merge needs a 2-D bfloat16 weight, got {w.dtype} {tuple(w.shape)}")
+        n_out, k_in = w.shape
+        a = stand_in.setdefault(n_out, torch.empty((n_out, 2 * RANK_PAD), dtype=BF16))
+        b = stand_in.setdefault(k_in, torch.empty((k_in, 2 * RANK_PAD), dtype=BF16))
+        # (a K that is no multiple of 8 is merged in a widened copy, ``merged_weight``)
+        c = w.detach() if k_in % 8 == 0 else torch.empty((n_out, (k_in + 7) // 8 * 8), dtype=BF16)
+        if k_in % 8:
+            b = torch.empty((c.shape[1], 2 * RANK_PAD), dtype=BF16)
+        kernel = ops.gemm_kernel_id(a, b, None, c, ops.EPI_GATE_RESIDUAL, c)
+        if kernel < 0:
+            raise ValueError(f"ltxmi.lora: '{path}' {(n_out, k_in)} (leading dimension {w.stride(0)}) cannot be merged: the GEMM "
+                             f"refuses it ({kernel}): {ops.lib.ltxmi_last_error().decode()}")
+
+
+def fused_entries(st, path):
+    """[(down, up, s)] of every fused adapter that names ``path``, in insertion order."""
+    out = []
+    for adapter, weight, paths in st.adapters.values():
+        if path in adapter.modules and path in paths:
+            down, up, _ = adapter.modules[path]
+            out.append((down, up, adapter.scale(path, weight)))
+    return out
+
+
+def remerge(model, paths, keep_base=True):
+    """Each linear of ``paths`` from its base copy with all fused adapters that name it, in one rounding; a linear no fused
+    adapter names any more gets its base bits back and its copy is freed.  ``keep_base=False``: the copy is dropped after the
+    merge (in place where none existed) and the linear is sealed."""
+    st = fused_state(model)
+    with torch.no_grad():
+        for path in paths:
+            weight = _get(model, path).weight
+            entries = fused_entries(st, path)
+            base = st.base.get(path)
+            if not entries:
+                if base is not None:
+                    weight.copy_(base)
+                    del st.base[path]
+                continue
+            if base is None:
+                if keep_base:
+                    base = st.base[path] = weight.detach().clone()
+                else:
+                    base = weight.detach()
+            merged_weight(base, entries, out=weight.detach(), what=path)
+            _touch(model, path, weight)
+            if not keep_base:
+                st.base.pop(path, None)
+                st.sealed.add(path)

@@ -153,6 +153,12 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         if any(k.startswith("model.diffusion_model.") for k in state_dict.keys()):
             state_dict = {k.replace("model.diffusion_model.", ""): v for k, v in state_dict.items()
                           if k.startswith("model.diffusion_model.")}
+        st = lora.fused_state(self)
+        if st is not None:
+            if st.adapters and st.base:
+                # the base copies would be those of the weights being replaced
+                raise RuntimeError("unfuse_lora() first")
+            del self.__dict__["_lora_fused"]         # only keep_base=False merges: the load replaces them, nothing is owed
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------ LoRA adapters (ltxmi/lora.py)
@@ -206,8 +212,83 @@ class Transformer3DModel(DerivedOwner, nn.Module):
     def lora_names(self):
         return list(self.__dict__.get("_lora_adapters") or {})
 
+    # ------------------------------------------------------------------ LoRA adapters fused into the weights
+    def fuse_lora(self, adapter, weight: float = 1.0, name: Optional[str] = None, keep_base: bool = True):
+        """Fold ``adapter`` (``loading.load_lora``) into the weight of every linear it names, at strength ``weight``: the
+        forward afterwards is the forward of a model without adapters, on ``bf16(W + sum s B A)`` -- one rounding, from an
+        fp32 sum that includes the base weight, for ALL fused adapters of a linear together (``lora.merged_weight``).  Every
+        linear of the model may be named, the seven outside the blocks included.  ``keep_base=True`` keeps a bf16 copy of the
+        base weight of each fused linear, which is what ``unfuse_lora``, ``set_fused_lora_weights`` and a further
+        ``fuse_lora`` on the same linear merge from; ``keep_base=False`` merges in place and keeps nothing, and those three
+        then raise for the linears concerned.  Fused and attached adapters may coexist: the attached ones run on top."""
+        paths = lora.fuse_paths(self, adapter)
+        st = lora.fused_state(self)
+        fused = st.adapters if st else {}
+        if name is None:
+            name = f"lora{len(fused)}"
+            while name in fused:
+                name += "_"
+        if name in fused:
+            raise ValueError(f"ltxmi: an adapter named '{name}' is fused already")
+        self._refuse_sealed(paths, "fuse_lora")
+        lora.check_mergeable(self, paths)                # before the first weight is written
+        st = lora.fused_state(self, create=True)
+        st.adapters[name] = [adapter, float(weight), paths]
+        try:
+            lora.remerge(self, paths, keep_base=keep_base)
+        except Exception:
+            if not st.sealed.intersection(paths):        # (nothing merged in place yet: back to the state before the call)
+                del st.adapters[name]
+                lora.remerge(self, paths)
+            raise
+
+    def _refuse_sealed(self, paths, what):
+        st = lora.fused_state(self)
+        gone = sorted(st.sealed.intersection(paths)) if st else []
+        if gone:
+            raise RuntimeError(f"ltxmi: {what}: an adapter was fused with keep_base=False into {gone[0]}"
+                               + (f" and {len(gone) - 1} more linears" if len(gone) > 1 else "")
+                               + "; the base weight is gone, so nothing can be merged from it again -- reload the checkpoint")
+
+    def set_fused_lora_weights(self, weights: Dict[str, float]):
+        """New strengths for fused adapters, by name: the linears they name are merged again from their bases, and hold the
+        bits a fresh ``fuse_lora`` at those strengths gives."""
+        st = lora.fused_state(self)
+        fused = st.adapters if st else {}
+        for name in weights:
+            if name not in fused:
+                raise KeyError(f"ltxmi: no adapter named '{name}' is fused")
+        paths = list(dict.fromkeys(p for name in weights for p in fused[name][2]))
+        self._refuse_sealed(paths, "set_fused_lora_weights")
+        for name, w in weights.items():
+            fused[name][1] = float(w)
+        lora.remerge(self, paths)
+
+    def unfuse_lora(self, name: Optional[str] = None):
+        """Remove one fused adapter, or all of them, and merge what remains again; a linear no fused adapter names any more
+        gets its base weight back bit for bit, and its base copy is freed."""
+        st = lora.fused_state(self)
+        fused = st.adapters if st else {}
+        if name is not None and name not in fused:
+            raise KeyError(f"ltxmi: no adapter named '{name}' is fused")
+        names = list(fused) if name is None else [name]
+        paths = list(dict.fromkeys(p for n in names for p in fused[n][2]))
+        self._refuse_sealed(paths, "unfuse_lora")
+        for n in names:
+            del fused[n]
+        lora.remerge(self, paths)
+        if st is not None and not st.adapters and not st.sealed:
+            del self.__dict__["_lora_fused"]
+
+    def fused_lora_names(self):
+        st = lora.fused_state(self)
+        return list(st.adapters) if st else []
+
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)
+        st = lora.fused_state(self)
+        if st is not None:
+            st.base = {path: fn(t) for path, t in st.base.items()}     # the base copies follow the weights (no parameters, no buffers)
         if self.__dict__.get("_lora_adapters"):
             lora.rebuild(self)                   # the per-linear state follows the weights' device
         return out
