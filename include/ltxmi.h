@@ -26,7 +26,7 @@
  *     0.8: no field -- ltxmi_norm_modulate_f32in_bf16 and ltxmi_gate_residual_f32, the row passes of the fp32 residual stream;
  *     0.9: no field -- pad_replicate = 2, ltxmi_gemm_pair2_bf16 / ltxmi_gemm_pair2_kernel_id with a struct of their own, and the T5
  *     encoder's entries ltxmi_attention_relbias_bf16 (a struct of its own), ltxmi_rmsnorm_weight_bf16, ltxmi_gated_gelu_bf16,
- *     ltxmi_embedding_bf16),
+ *     ltxmi_embedding_bf16; also 0.9: LTXMI_VERSION and the named id enums; no field, no prototype),
  *     and a zero there means "off".  A caller must be
  *     rebuilt against the header of the library it loads.  An optional pointer that is NULL
  *     switches its companion size / stride fields off whatever they hold.
@@ -48,7 +48,9 @@ typedef enum ltxmi_status {
     LTXMI_ERR_LAUNCH = -3         /* hipGetLastError() != hipSuccess after the launch     */
 } ltxmi_status;
 
-/* Library identification and error text. */
+/* Library identification and error text.  ltxmi_version() returns "ltxmi " LTXMI_VERSION: a caller built against (or, as the
+ * Python binding, read from) this header refuses a library that answers anything else. */
+#define LTXMI_VERSION "0.9.0"
 const char* ltxmi_version(void);
 const char* ltxmi_last_error(void);
 /* Name of the gfx target the kernels were compiled for ("gfx950"). */
@@ -118,6 +120,10 @@ int ltxmi_gemm_bf16(const ltxmi_gemm_args* args, void* stream);
  * (if any) is 16-byte aligned with ldr % 8 == 0 and M * ldr * 2 < 2^32; id 1 when only the first three hold; else id 0.
  * algo = 128 / 256 give id 0 / 1 for every accepted shape.  Every kernel accumulates over K in the same order: for the same
  * arguments the three produce the same bits. */
+typedef enum ltxmi_gemm_kernel {   /* the ids of ltxmi_gemm_kernel_id (0 .. 2) and ltxmi_gemm_pair2_kernel_id (3, 4) */
+    LTXMI_GEMM_TILE128 = 0, LTXMI_GEMM_TILE256 = 1, LTXMI_GEMM_PERSISTENT256 = 2,
+    LTXMI_GEMM_PAIR2_TILE128 = 3, LTXMI_GEMM_PAIR2_TILE256 = 4
+} ltxmi_gemm_kernel;
 int ltxmi_gemm_kernel_id(const ltxmi_gemm_args* args);
 
 /* ---------------------------------------------------------------------------------
@@ -392,12 +398,13 @@ int ltxmi_stg_blend_grouped_bf16(void* a, const void* v, int64_t v_stride_g, int
  *   the pixel-shuffled, channel-repeated input is added (res_repeat = 8 / reduction).
  * Cin % 64 == 0; Cout % 8 == 0.
  * ------------------------------------------------------------------------------- */
+typedef enum ltxmi_pad_mode { LTXMI_PAD_ZEROS = 0, LTXMI_PAD_REPLICATE = 1, LTXMI_PAD_REFLECT = 2 } ltxmi_pad_mode;
 typedef struct ltxmi_conv3d_args {
     const void* x; const void* w; const void* bias; void* y;
     int32_t B, T, H, W, Cin, Cout;
     int32_t causal;            /* 1: replicate 2 frames in front; 0: 1 + 1                */
     int32_t pad_replicate;     /* spatial padding MODE (the name is older than the third value): 0 zeros, 1 replicate,
-                                  2 reflect (0.9); anything else, or reflect with H < 2 or W < 2, is
+                                  2 reflect (0.9) -- ltxmi_pad_mode; anything else, or reflect with H < 2 or W < 2, is
                                   LTXMI_ERR_INVALID_ARG                                    */
     int32_t d2s;               /* 0 plain NDHWC store, 1 depth-to-space (2,2,2) store     */
     const void* residual;      /* d2s only: x itself (pre-conv block input) or NULL       */
@@ -466,8 +473,11 @@ int64_t ltxmi_conv3d_workspace_bytes(const ltxmi_conv3d_args* args);
  * ltxmi_conv3d_workspace_bytes() means the unsplit route).  Returns the status the launch would return (0, or the negative
  * ltxmi_status with ltxmi_last_error() saying why; *out then holds route = -1 and zeros).  0.7 also moves the refusal of `add`
  * together with d2s (LTXMI_ERR_INVALID_ARG) from the implicit GEMM's launcher into that check. */
+typedef enum ltxmi_conv_route {
+    LTXMI_CONV_GEMM128 = 0, LTXMI_CONV_GEMM256 = 1, LTXMI_CONV_DIRECT8 = 2, LTXMI_CONV_DIRECT4 = 3
+} ltxmi_conv_route;
 typedef struct ltxmi_conv3d_route_info {
-    int32_t route;            /* 0 implicit GEMM, 128 x 128 tiles; 1 implicit GEMM, 256 x 256 tiles; 2 direct convolution,
+    int32_t route;            /* ltxmi_conv_route: 0 implicit GEMM, 128 x 128 tiles; 1 implicit GEMM, 256 x 256 tiles; 2 direct convolution,
                                  eight waves per workgroup; 3 direct convolution, four waves per workgroup                    */
     int32_t epilogue;         /* the epilogue the convolution kernel is launched with: 0 plain store, 1 + add, 2 depth-to-space
                                  (every route); the four-wave direct form also 3 / 4 / 5 = 0 / 1 / 2 with post_norm applied
@@ -624,7 +634,8 @@ int ltxmi_pixel_shuffle_nd_ndhwc_bf16(const void* x, void* y, int32_t B, int32_t
 /* Tile cross-fade of the tiled VAE decode / encode (blend_z / blend_v / blend_h, vae.py:193-221), in place in b:
  *   b[o, z, i] = a[o, len_a - extent + z, i] * (1 - z / extent) + b[o, z, i] * (z / extent),   z < extent,
  * both tensors contiguous and viewed as [outer][len][inner] around the blended axis; dtype: 0 fp32, 1 bf16, 2 fp16 (the
- * reference keeps z-tiles in fp16, vae.py:388). */
+ * reference keeps z-tiles in fp16, vae.py:388) -- ltxmi_blend_dtype. */
+typedef enum ltxmi_blend_dtype { LTXMI_BLEND_F32 = 0, LTXMI_BLEND_BF16 = 1, LTXMI_BLEND_F16 = 2 } ltxmi_blend_dtype;
 int ltxmi_tile_blend(const void* a, void* b, int32_t dtype, int64_t outer, int64_t len_a, int64_t len_b,
                      int64_t inner, int32_t extent, void* stream);
 int ltxmi_adain_filter(const void* latents, const void* reference, void* out, int32_t is_bf16, int32_t planes,

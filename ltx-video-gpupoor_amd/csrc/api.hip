@@ -65,6 +65,6 @@ int device_cu_count(const char* what) {
 
 }  // namespace ltxmi
 
-extern "C" const char* ltxmi_version(void) { return "ltxmi 0.9.0"; }
+extern "C" const char* ltxmi_version(void) { return "ltxmi " LTXMI_VERSION; }
 extern "C" const char* ltxmi_last_error(void) { return ltxmi::g_err; }
 extern "C" const char* ltxmi_arch(void) { return "gfx950"; }

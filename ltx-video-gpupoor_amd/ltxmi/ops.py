@@ -14,8 +14,14 @@ from ._lib import lib, check
 
 BF16 = torch.bfloat16
 
-EPI_NONE, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RESIDUAL = 0, 1, 2, 3
-NORM_RMS, NORM_LAYER = 0, 1
+
+def _header(*names):
+    """The values of include/ltxmi.h's enum constants and defines LTXMI_<name>: no number of the header is restated here."""
+    return tuple(_lib.CONSTANTS["LTXMI_" + n] for n in names)
+
+
+EPI_NONE, EPI_GELU_TANH, EPI_SILU, EPI_GATE_RESIDUAL = _header("EPI_NONE", "EPI_GELU_TANH", "EPI_SILU", "EPI_GATE_RESIDUAL")
+NORM_RMS, NORM_LAYER = _header("NORM_RMS", "NORM_LAYER")
 
 
 def _stream():
@@ -195,8 +201,9 @@ def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table
     return out
 
 
-GEMM_TILE128, GEMM_TILE256, GEMM_PERSISTENT256 = 0, 1, 2      # include/ltxmi.h: ltxmi_gemm_kernel_id
-GEMM_PAIR2_TILE128, GEMM_PAIR2_TILE256 = 3, 4                  # ... ltxmi_gemm_pair2_kernel_id
+# ltxmi_gemm_kernel: what ltxmi_gemm_kernel_id and ltxmi_gemm_pair2_kernel_id answer
+GEMM_TILE128, GEMM_TILE256, GEMM_PERSISTENT256 = _header("GEMM_TILE128", "GEMM_TILE256", "GEMM_PERSISTENT256")
+GEMM_PAIR2_TILE128, GEMM_PAIR2_TILE256 = _header("GEMM_PAIR2_TILE128", "GEMM_PAIR2_TILE256")
 
 
 def gemm_kernel_id(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
@@ -216,44 +223,42 @@ def gemm_kernel_id(a, w, bias=None, out=None, epilogue=EPI_NONE, residual=None, 
     return int(lib.ltxmi_gemm_pair2_kernel_id(ctypes.byref(args), ctypes.byref(pair)))
 
 
-def norm_modulate(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):
-    """out = norm(x) * (1 + scale_table + scale_temb[g]) + shift_table + shift_temb[g].
-    scale_temb/shift_temb: 2-D views [groups, D] sharing one row stride."""
-    _chk_bf16(x, out, scale_table, scale_temb, shift_table, shift_temb)
-    x2, rows, ldx = _rows(x)
-    o2, _, ldy = _rows(out)
-    D = x2.shape[1]
-    if scale_temb.stride(0) != shift_temb.stride(0):
-        raise ValueError("ltxmi.norm_modulate: scale/shift tables must share a row stride")
-    check(lib.ltxmi_norm_modulate_bf16(_ptr(x2), ldx, _ptr(o2), ldy, rows, D, eps, kind,
-                                       _ptr(scale_table), _ptr(scale_temb), _ptr(shift_table), _ptr(shift_temb),
-                                       scale_temb.stride(0), rows_per_group, _stream()),
-          "ltxmi_norm_modulate_bf16")
-    return out
-
-
 def _chk_f32(t, what):
     if t.dtype != torch.float32 or not t.is_cuda:
         raise TypeError(f"ltxmi.{what}: expected a CUDA float32 tensor, got {t.dtype} on {t.device}")
 
 
-def norm_modulate_f32in(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):
-    """``norm_modulate`` for the fp32 residual stream (mixed precision): x fp32 rows, out bf16 rows, the statistics and the
-    modulation in fp32 from the unrounded stream, one rounding at the store (include/ltxmi.h)."""
-    _chk_f32(x, "norm_modulate_f32in")
-    _chk_bf16(out, scale_table, scale_temb, shift_table, shift_temb)
+def _norm_modulate(what, f32in, x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):
+    """The one body of ``norm_modulate`` and ``norm_modulate_f32in``: x's dtype and the entry point are what differs."""
+    if f32in:
+        _chk_f32(x, what)
+    _chk_bf16(None if f32in else x, out, scale_table, scale_temb, shift_table, shift_temb)
     x2, rows, ldx = _rows(x)
     o2, orows, ldy = _rows(out)
     D = x2.shape[1]
-    if orows != rows or o2.shape[1] != D:
-        raise ValueError("ltxmi.norm_modulate_f32in: out must have x's rows and channels")
+    if f32in and (orows != rows or o2.shape[1] != D):     # (the bf16 entry has never tested out's shape: left as it was)
+        raise ValueError(f"ltxmi.{what}: out must have x's rows and channels")
     if scale_temb.stride(0) != shift_temb.stride(0):
-        raise ValueError("ltxmi.norm_modulate_f32in: scale/shift tables must share a row stride")
-    check(lib.ltxmi_norm_modulate_f32in_bf16(_ptr(x2), ldx, _ptr(o2), ldy, rows, D, eps, kind,
-                                             _ptr(scale_table), _ptr(scale_temb), _ptr(shift_table), _ptr(shift_temb),
-                                             scale_temb.stride(0), rows_per_group, _stream()),
-          "ltxmi_norm_modulate_f32in_bf16")
+        raise ValueError(f"ltxmi.{what}: scale/shift tables must share a row stride")
+    entry = lib.ltxmi_norm_modulate_f32in_bf16 if f32in else lib.ltxmi_norm_modulate_bf16
+    check(entry(_ptr(x2), ldx, _ptr(o2), ldy, rows, D, eps, kind, _ptr(scale_table), _ptr(scale_temb), _ptr(shift_table),
+                _ptr(shift_temb), scale_temb.stride(0), rows_per_group, _stream()),
+          "ltxmi_norm_modulate_f32in_bf16" if f32in else "ltxmi_norm_modulate_bf16")
     return out
+
+
+def norm_modulate(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):
+    """out = norm(x) * (1 + scale_table + scale_temb[g]) + shift_table + shift_temb[g].
+    scale_temb/shift_temb: 2-D views [groups, D] sharing one row stride."""
+    return _norm_modulate("norm_modulate", False, x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb,
+                          rows_per_group)
+
+
+def norm_modulate_f32in(x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group):
+    """``norm_modulate`` for the fp32 residual stream (mixed precision): x fp32 rows, out bf16 rows, the statistics and the
+    modulation in fp32 from the unrounded stream, one rounding at the store (include/ltxmi.h)."""
+    return _norm_modulate("norm_modulate_f32in", True, x, out, eps, kind, scale_table, scale_temb, shift_table, shift_temb,
+                          rows_per_group)
 
 
 def gate_residual_f32_(h, y, gate_table=None, gate_temb=None, rows_per_group=1, round_product=0, h_bf16=None):
@@ -336,6 +341,34 @@ def attention_kernel_id(B, H, Lq, Lk, dh, has_key_bias=False, k_stride_l=None, v
     return int(lib.ltxmi_attention_kernel_id(B, H, Lq, Lk, dh, int(has_key_bias), ks, vs))
 
 
+def _attn_shared(a, what, cuda_bias, dims, q, k, v, out, key_bias, softmax_scale):
+    """The twenty leading fields that ltxmi_attn_args and ltxmi_attn_relbias_args have in common (the second is a prefix of
+    the first by design), after ``_chk_attn_qkv``.  ``out`` has been tested by the caller: its shape is where the two
+    contracts differ (``attention``'s out_segments), and so do the error texts."""
+    B, H, Lq, Lk, dh = dims
+    a.q, a.q_stride_b, a.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
+    a.k, a.k_stride_b, a.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
+    a.v, a.v_stride_b, a.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
+    a.o, a.o_stride_b, a.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    if key_bias is not None:
+        if key_bias.dtype != torch.float32 or key_bias.shape != (B, Lk) or key_bias.stride(1) != 1 \
+                or (cuda_bias and not key_bias.is_cuda):
+            raise ValueError(f"ltxmi.{what}: key_bias must be {'a CUDA ' if cuda_bias else ''}fp32 [B, Lk]")
+        a.key_bias, a.bias_stride_b = key_bias.data_ptr(), key_bias.stride(0)
+    a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, dh
+    a.softmax_scale = softmax_scale
+
+
+def _chk_attn_qkv(what, q, k, v, out):
+    """The tests ``attention`` and ``attention_relbias`` make before anything else -> (B, H, Lq, Lk, dh)."""
+    _chk_bf16(q, k, v, out)
+    B, Lq, H, dh = q.shape
+    for t in (q, k, v):
+        if t.stride(3) != 1 or t.stride(2) != dh:
+            raise ValueError(f"ltxmi.{what}: (heads, head_dim) must be contiguous")
+    return B, H, Lq, k.shape[1], dh
+
+
 def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None, rope=None, out_segments=None,
               redo_counter=None, force_exact=False, return_lse=False, lse=None):
     """q [B,Lq,H,dh], k/v [B,Lk,H,dh] (NHD; batch and token strides free, (H,dh) contiguous).
@@ -353,12 +386,7 @@ def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None,
     ``out`` was divided by (-inf for a row with every key removed) -- allocated here or written into ``lse=`` (which
     implies return_lse); ``attention_merge`` combines such pairs over disjoint key sets.  ``out`` and the kernel chosen do
     not depend on it."""
-    _chk_bf16(q, k, v, out)
-    B, Lq, H, dh = q.shape
-    Lk = k.shape[1]
-    for t in (q, k, v):
-        if t.stride(3) != 1 or t.stride(2) != dh:
-            raise ValueError("ltxmi.attention: (heads, head_dim) must be contiguous")
+    B, H, Lq, Lk, dh = dims = _chk_attn_qkv("attention", q, k, v, out)
     if out is None:
         if out_segments is not None:
             raise ValueError("ltxmi.attention: out_segments needs an explicit out")
@@ -374,16 +402,8 @@ def attention(q, k, v, out=None, key_bias=None, softmax_scale=None, q_norm=None,
         a.o_segment_len, a.o_stride_segment = seg_len, seg_stride
     elif tuple(out.shape) != (B, Lq, H, dh):
         raise ValueError(f"ltxmi.attention: out must be [B, Lq, H, dh] = {(B, Lq, H, dh)}, got {tuple(out.shape)}")
-    a.q, a.q_stride_b, a.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
-    a.k, a.k_stride_b, a.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
-    a.v, a.v_stride_b, a.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
-    a.o, a.o_stride_b, a.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
-    if key_bias is not None:
-        if key_bias.dtype != torch.float32 or key_bias.shape != (B, Lk) or key_bias.stride(1) != 1:
-            raise ValueError("ltxmi.attention: key_bias must be fp32 [B, Lk]")
-        a.key_bias, a.bias_stride_b = key_bias.data_ptr(), key_bias.stride(0)
-    a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, dh
-    a.softmax_scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(dh)
+    _attn_shared(a, "attention", False, dims, q, k, v, out, key_bias,
+                 softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(dh))
     if q_norm is not None:
         ss, w, eps = q_norm
         nb = H * dh // 64
@@ -559,7 +579,7 @@ _conv_workspace = {}
 
 
 # conv3d(pad_replicate=...): the spatial padding mode, ltxmi_conv3d_args.pad_replicate (False / True are the first two)
-PAD_ZEROS, PAD_REPLICATE, PAD_REFLECT = 0, 1, 2
+PAD_ZEROS, PAD_REPLICATE, PAD_REFLECT = _header("PAD_ZEROS", "PAD_REPLICATE", "PAD_REFLECT")
 
 
 def _conv3d_args(x, w_packed, bias, causal, pad_replicate, d2s, residual, add, out, stride, tpad, out_T, kernel_t,
@@ -678,8 +698,8 @@ def conv3d(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, a
     return (out, out_norm) if keep_raw else out
 
 
-# include/ltxmi.h: ltxmi_conv3d_route_info.route
-CONV_GEMM128, CONV_GEMM256, CONV_DIRECT8, CONV_DIRECT4 = 0, 1, 2, 3
+# ltxmi_conv_route: ltxmi_conv3d_route_info.route
+CONV_GEMM128, CONV_GEMM256, CONV_DIRECT8, CONV_DIRECT4 = _header("CONV_GEMM128", "CONV_GEMM256", "CONV_DIRECT8", "CONV_DIRECT4")
 
 
 def conv3d_route(x, w_packed, bias, causal, pad_replicate, d2s=False, residual=None, add=None, out=None,
@@ -794,31 +814,41 @@ def set_step_invariant_caching(enabled: bool):
     STEP_INVARIANT_CACHING = bool(enabled)
 
 
-GUIDANCE_WORKSPACE_FLOATS = 2048      # include/ltxmi.h: LTXMI_GUIDANCE_WORKSPACE_FLOATS
+GUIDANCE_WORKSPACE_FLOATS, = _header("GUIDANCE_WORKSPACE_FLOATS")
+
+
+def _chk_guidance(what, noise_pred, latents, workspace, cond_mask, batched):
+    """The tests ``guidance_step_`` (one video: b = 1 whatever latents' leading dimension) and ``guidance_step_batched_``
+    share -> (b, num_conds, n, C, is_bf16)."""
+    _chk_bf16(noise_pred)
+    is_bf16 = latents.dtype == BF16
+    if not is_bf16 and latents.dtype != torch.float32:
+        raise TypeError(f"ltxmi.{what}: latents must be fp32 or bf16")
+    b = latents.shape[0] if batched else 1
+    if batched and (latents.dim() != 3 or noise_pred.dim() != 3 or not noise_pred.is_contiguous() or noise_pred.shape[0] % b != 0):
+        raise ValueError(f"ltxmi.{what}: noise_pred must be contiguous [num_conds * b, N, C] for latents [b, N, C]")
+    n = noise_pred[0].numel()
+    if not latents.is_contiguous() or latents.numel() != b * n:
+        raise ValueError(f"ltxmi.{what}: latents must be contiguous and match one chunk of noise_pred")
+    if workspace.dtype != torch.float32 or workspace.numel() < b * GUIDANCE_WORKSPACE_FLOATS:
+        raise ValueError(f"ltxmi.{what}: workspace must hold {f'{b} x ' if batched else ''}{GUIDANCE_WORKSPACE_FLOATS} fp32 values")
+    C = noise_pred.shape[-1]
+    if cond_mask is not None and (cond_mask.dtype != torch.float32 or not cond_mask.is_contiguous()
+                                  or cond_mask.numel() * C != b * n):
+        raise ValueError(f"ltxmi.{what}: cond_mask must be contiguous fp32 with one value per token")
+    return b, noise_pred.shape[0] // b, n, C, is_bf16
 
 
 def guidance_step_(noise_pred, latents, dt, guidance_scale, stg_scale, rescaling_scale, do_cfg, do_stg, do_rescale,
                    workspace, cond_mask=None, t=0.0):
     """noise_pred bf16 [num_conds, N, C] (one sample); latents fp32/bf16 [1, N, C], updated in place.
     cond_mask fp32 [1, N] (or None): only tokens with t - 1e-6 < 1 - cond_mask are advanced."""
-    _chk_bf16(noise_pred)
-    num_conds = noise_pred.shape[0]
-    n = noise_pred[0].numel()
-    is_bf16 = latents.dtype == BF16
-    if not is_bf16 and latents.dtype != torch.float32:
-        raise TypeError("ltxmi.guidance_step_: latents must be fp32 or bf16")
-    if not latents.is_contiguous() or latents.numel() != n:
-        raise ValueError("ltxmi.guidance_step_: latents must be contiguous and match one chunk of noise_pred")
-    if workspace.dtype != torch.float32 or workspace.numel() < GUIDANCE_WORKSPACE_FLOATS:
-        raise ValueError(f"ltxmi.guidance_step_: workspace must hold {GUIDANCE_WORKSPACE_FLOATS} fp32 values")
+    _, num_conds, n, C, is_bf16 = _chk_guidance("guidance_step_", noise_pred, latents, workspace, cond_mask, False)
     if cond_mask is None:
         check(lib.ltxmi_guidance_step_bf16(_ptr(noise_pred), n, num_conds, guidance_scale, stg_scale, rescaling_scale,
                                            int(do_cfg), int(do_stg), int(do_rescale), _ptr(latents), int(is_bf16),
                                            float(dt), _ptr(workspace), _stream()), "ltxmi_guidance_step_bf16")
         return latents
-    C = noise_pred.shape[-1]
-    if cond_mask.dtype != torch.float32 or not cond_mask.is_contiguous() or cond_mask.numel() * C != n:
-        raise ValueError("ltxmi.guidance_step_: cond_mask must be contiguous fp32 with one value per token")
     check(lib.ltxmi_guidance_step_masked_bf16(_ptr(noise_pred), n, num_conds, guidance_scale, stg_scale,
                                               rescaling_scale, int(do_cfg), int(do_stg), int(do_rescale),
                                               _ptr(latents), int(is_bf16), float(dt), _ptr(cond_mask), C, float(t),
@@ -832,23 +862,7 @@ def guidance_step_batched_(noise_pred, latents, dt, guidance_scale, stg_scale, r
     perturbed x b); latents fp32/bf16 [b, N, C], updated in place; cond_mask fp32 [b, N] (or None); workspace fp32 of at
     least b * GUIDANCE_WORKSPACE_FLOATS values.  Video j gets the bits ``guidance_step_`` gives for noise_pred[j::b],
     latents[j:j + 1], cond_mask[j:j + 1]: every sum of the guidance is per video."""
-    _chk_bf16(noise_pred)
-    is_bf16 = latents.dtype == BF16
-    if not is_bf16 and latents.dtype != torch.float32:
-        raise TypeError("ltxmi.guidance_step_batched_: latents must be fp32 or bf16")
-    b = latents.shape[0]
-    if latents.dim() != 3 or noise_pred.dim() != 3 or not noise_pred.is_contiguous() or noise_pred.shape[0] % b != 0:
-        raise ValueError("ltxmi.guidance_step_batched_: noise_pred must be contiguous [num_conds * b, N, C] for latents [b, N, C]")
-    num_conds = noise_pred.shape[0] // b
-    n = noise_pred[0].numel()
-    if not latents.is_contiguous() or latents.numel() != b * n:
-        raise ValueError("ltxmi.guidance_step_batched_: latents must be contiguous and match one chunk of noise_pred")
-    if workspace.dtype != torch.float32 or workspace.numel() < b * GUIDANCE_WORKSPACE_FLOATS:
-        raise ValueError(f"ltxmi.guidance_step_batched_: workspace must hold {b} x {GUIDANCE_WORKSPACE_FLOATS} fp32 values")
-    C = noise_pred.shape[-1]
-    if cond_mask is not None and (cond_mask.dtype != torch.float32 or not cond_mask.is_contiguous()
-                                  or cond_mask.numel() * C != b * n):
-        raise ValueError("ltxmi.guidance_step_batched_: cond_mask must be contiguous fp32 with one value per token")
+    b, num_conds, n, C, is_bf16 = _chk_guidance("guidance_step_batched_", noise_pred, latents, workspace, cond_mask, True)
     check(lib.ltxmi_guidance_step_batched_bf16(_ptr(noise_pred), b, n, num_conds, guidance_scale, stg_scale,
                                                rescaling_scale, int(do_cfg), int(do_stg), int(do_rescale),
                                                _ptr(latents), int(is_bf16), float(dt),
@@ -941,11 +955,14 @@ def adain_filter(latents, reference, factor=1.0):
     return out
 
 
+BLEND_F32, BLEND_BF16, BLEND_F16 = _header("BLEND_F32", "BLEND_BF16", "BLEND_F16")      # ltxmi_blend_dtype
+
+
 def tile_blend_(a, b, extent, dim):
     """In place in ``b``: the first ``extent`` slices of ``b`` along ``dim`` cross-faded with the last ``extent`` of ``a``
     (blend_z / blend_v / blend_h, vae.py:193-221).  a, b: contiguous, same dtype (fp32 or bf16), equal sizes on every
     other axis."""
-    codes = {torch.float32: 0, BF16: 1, torch.float16: 2}
+    codes = {torch.float32: BLEND_F32, BF16: BLEND_BF16, torch.float16: BLEND_F16}
     if a.dtype != b.dtype or b.dtype not in codes:
         raise TypeError("ltxmi.tile_blend_: fp32, bf16 or fp16 tensors of the same dtype expected")
     if not (a.is_contiguous() and b.is_contiguous()):
@@ -974,32 +991,18 @@ def attention_relbias(q, k, v, rel_bias=None, rel_center=0, key_bias=None, softm
     rel_bias: fp32 [H, >= rel_center + Lk], the value for head h and offset d = key - query at ``rel_bias[h, rel_center +
     d]``, rel_center >= Lq - 1; None: no relative bias, the call is ``attention``'s.  key_bias: fp32 [B, Lk] with the
     contract of ``attention`` (at or below -1e30 removes the key).  T5 does not scale its scores: softmax_scale = 1."""
-    _chk_bf16(q, k, v, out)
-    B, Lq, H, dh = q.shape
-    Lk = k.shape[1]
-    for t in (q, k, v):
-        if t.stride(3) != 1 or t.stride(2) != dh:
-            raise ValueError("ltxmi.attention_relbias: (heads, head_dim) must be contiguous")
+    B, H, Lq, Lk, dh = dims = _chk_attn_qkv("attention_relbias", q, k, v, out)
     if out is None:
         out = torch.empty((B, Lq, H, dh), dtype=BF16, device=q.device)
     if tuple(out.shape) != (B, Lq, H, dh) or out.stride(3) != 1 or out.stride(2) != dh:
         raise ValueError(f"ltxmi.attention_relbias: out must be [B, Lq, H, dh] = {(B, Lq, H, dh)} with (heads, head_dim) contiguous")
     a = _lib.AttnRelBiasArgs()
-    a.q, a.q_stride_b, a.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
-    a.k, a.k_stride_b, a.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
-    a.v, a.v_stride_b, a.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
-    a.o, a.o_stride_b, a.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
-    if key_bias is not None:
-        if key_bias.dtype != torch.float32 or key_bias.shape != (B, Lk) or key_bias.stride(1) != 1 or not key_bias.is_cuda:
-            raise ValueError("ltxmi.attention_relbias: key_bias must be a CUDA fp32 [B, Lk]")
-        a.key_bias, a.bias_stride_b = key_bias.data_ptr(), key_bias.stride(0)
+    _attn_shared(a, "attention_relbias", True, dims, q, k, v, out, key_bias, float(softmax_scale))
     if rel_bias is not None:
         if rel_bias.dtype != torch.float32 or rel_bias.dim() != 2 or rel_bias.shape[0] != H or rel_bias.stride(1) != 1 \
                 or not rel_bias.is_cuda or rel_bias.shape[1] < rel_center + Lk:
             raise ValueError("ltxmi.attention_relbias: rel_bias must be a CUDA fp32 [H, >= rel_center + Lk]")
         a.rel_bias, a.rel_stride_h, a.rel_center = rel_bias.data_ptr(), rel_bias.stride(0), rel_center
-    a.B, a.H, a.Lq, a.Lk, a.head_dim = B, H, Lq, Lk, dh
-    a.softmax_scale = float(softmax_scale)
     tok = _prof_begin(("attention_relbias", B, H, Lq, Lk, dh))
     check(lib.ltxmi_attention_relbias_bf16(ctypes.byref(a), _stream()), "ltxmi_attention_relbias_bf16")
     _prof_end(tok)

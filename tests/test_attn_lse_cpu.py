@@ -28,32 +28,22 @@ def test_merge_entry_point_is_exported_and_declared():
     text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     assert re.search(r"\bint\s+ltxmi_attention_merge_bf16\s*\(\s*const\s+ltxmi_attn_merge_args\s*\*", text)
     assert hasattr(_lib.lib, "ltxmi_attention_merge_bf16") and "ltxmi_attention_merge_bf16" in _lib.SIGNATURES
-
-
-def _struct_fields(text, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        first, *rest = decl.split(",")
-        names.append(re.sub(r"\[.*?\]", "", first).split()[-1].lstrip("*"))
-        names += [re.sub(r"\[.*?\]", "", r).strip().lstrip("*") for r in rest]
-    return names
+    assert _lib.SIGNATURES["ltxmi_attention_merge_bf16"] == (ctypes.c_int32, [ctypes.POINTER(_lib.AttnMergeArgs), ctypes.c_void_p])
 
 
 def test_ctypes_mirrors_match_the_header():
+    """The classes are read from the header (tests/test_abi_binding.py holds every field's offset and size against the
+    compiler's): what is left to say here is where the lse fields sit."""
     from ltxmi import _lib
-    text = open(HEADER).read()
-    attn = _struct_fields(text, "ltxmi_attn_args")
+    attn = [f[0] for f in _lib.AttnArgs._fields_]
     assert attn[-3:] == ["lse", "lse_stride_b", "lse_stride_h"]                     # appended at the tail
     assert attn[-5:-3] == ["redo_counter", "force_exact"]
-    assert [f[0] for f in _lib.AttnArgs._fields_] == attn
-    assert [f[0] for f in _lib.AttnMergeArgs._fields_] == _struct_fields(text, "ltxmi_attn_merge_args")
-    assert _lib.AttnArgs.lse.size == 8 and _lib.AttnArgs.lse_stride_b.size == 8
-    assert _lib.ATTN_MERGE_MAX == int(re.search(r"#define LTXMI_ATTN_MERGE_MAX (\d+)", text).group(1)) == 8
+    assert _lib.AttnArgs.lse_stride_h.offset + 8 == ctypes.sizeof(_lib.AttnArgs)     # ... of the struct itself, no padding behind
+    assert [f[0] for f in _lib.AttnMergeArgs._fields_][:7] == ["n", "o_part", "o_part_stride_b", "o_part_stride_l", "lse_part",
+                                                               "lse_part_stride_b", "lse_part_stride_h"]
+    assert _lib.AttnArgs.lse.size == 8 and _lib.AttnArgs.lse_stride_b.size == 8 and _lib.AttnArgs.lse_stride_h.size == 8
+    assert _lib.AttnMergeArgs.o_part.size == _lib.AttnMergeArgs.lse_part_stride_h.size == 8 * _lib.ATTN_MERGE_MAX
+    assert _lib.ATTN_MERGE_MAX == _lib.CONSTANTS["LTXMI_ATTN_MERGE_MAX"] == 8
 
 
 @pytest.mark.parametrize("case", ATTN_KERNEL_IDS, ids=lambda c: "x".join(map(str, c[:-1])))

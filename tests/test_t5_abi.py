@@ -99,6 +99,17 @@ def test_row_entries_refuse(case):
     assert word.encode() in _lib.lib.ltxmi_last_error()
 
 
+def test_relbias_args_begin_as_attn_args_do():
+    """ltxmi_attn_relbias_args is a prefix of ltxmi_attn_args by design (ops._attn_shared fills both): the same twenty
+    fields, types and offsets, then its own three."""
+    from ltxmi import _lib
+    rel, attn = _lib.AttnRelBiasArgs, _lib.AttnArgs
+    assert rel._fields_[:20] == attn._fields_[:20] and rel._fields_[19][0] == "softmax_scale"
+    assert [getattr(rel, n).offset for n, _ in rel._fields_[:20]] == [getattr(attn, n).offset for n, _ in attn._fields_[:20]]
+    assert [n for n, _ in rel._fields_[20:]] == ["rel_bias", "rel_stride_h", "rel_center"]
+    assert _lib.SIGNATURES["ltxmi_attention_relbias_bf16"] == (ctypes.c_int32, [ctypes.POINTER(rel), ctypes.c_void_p])
+
+
 def test_header_names_the_pipeline_lines_the_entries_serve():
     import os
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ltxmi.h")).read()
