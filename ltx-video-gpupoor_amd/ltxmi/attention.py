@@ -26,7 +26,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from . import lora, ops
+from . import ff_mx8, lora, ops
 from .attention_seam import pay_attention
 from .derived import DerivedOwner, cache_key
 
@@ -435,12 +435,18 @@ class BasicTransformerBlock(nn.Module):
         sc_t, sc_e = chunk(4)
         sh_t, sh_e = chunk(3)
         ops.norm_modulate(h2, norm_h.view(B * N, D), self.norm2.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
-        ff1 = ops.gemm(norm_h.view(B * N, D), self.ff.net[0].proj.weight, self.ff.net[0].proj.bias,
-                       epilogue=ops.EPI_GELU_TANH, **lora.pair(self.ff, "ff1", norm_h.view(B * N, D)))
-        del norm_h
         g_t, g_e = chunk(5)
-        ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=h2, epilogue=ops.EPI_GATE_RESIDUAL,
-                 residual=h2, gate_table=g_t, gate_temb=g_e, rows_per_group=rpg, **lora.pair(self.ff, "ff2", ff1))
+        if "_mx8" in self.ff.__dict__:               # Transformer3DModel.quantize_ff: the pair in MX-FP8 (ltxmi/ff_mx8.py)
+            ff1 = ff_mx8.ff1(self.ff, norm_h.view(B * N, D))
+            del norm_h
+            ff_mx8.ff2(self.ff, ff1, out=h2, epilogue=ops.EPI_GATE_RESIDUAL, residual=h2, gate_table=g_t, gate_temb=g_e,
+                       rows_per_group=rpg)
+        else:
+            ff1 = ops.gemm(norm_h.view(B * N, D), self.ff.net[0].proj.weight, self.ff.net[0].proj.bias,
+                           epilogue=ops.EPI_GELU_TANH, **lora.pair(self.ff, "ff1", norm_h.view(B * N, D)))
+            del norm_h
+            ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=h2, epilogue=ops.EPI_GATE_RESIDUAL,
+                     residual=h2, gate_table=g_t, gate_temb=g_e, rows_per_group=rpg, **lora.pair(self.ff, "ff2", ff1))
         del ff1
 
         if block_skip:
@@ -487,9 +493,13 @@ class BasicTransformerBlock(nn.Module):
         sc_t, sc_e = chunk(4)
         sh_t, sh_e = chunk(3)
         ops.norm_modulate_f32in(h2, norm_h, self.norm2.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
-        ff1 = ops.gemm(norm_h, self.ff.net[0].proj.weight, self.ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH,
-                       **lora.pair(self.ff, "ff1", norm_h))
-        ff2 = ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=norm_h, **lora.pair(self.ff, "ff2", ff1))
+        if "_mx8" in self.ff.__dict__:               # quantised pair; FF2's plain bf16 output feeds the fp32 row pass as before
+            ff1 = ff_mx8.ff1(self.ff, norm_h)
+            ff2 = ff_mx8.ff2(self.ff, ff1, out=norm_h)
+        else:
+            ff1 = ops.gemm(norm_h, self.ff.net[0].proj.weight, self.ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH,
+                           **lora.pair(self.ff, "ff1", norm_h))
+            ff2 = ops.gemm(ff1, self.ff.net[2].weight, self.ff.net[2].bias, out=norm_h, **lora.pair(self.ff, "ff2", ff1))
         del ff1
         g_t, g_e = chunk(5)
         ops.gate_residual_f32_(h2, ff2, g_t, g_e, rpg, round_product=0)

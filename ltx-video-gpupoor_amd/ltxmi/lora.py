@@ -266,6 +266,8 @@ def _touch(model, path, weight):
             owner = owner[int(p)] if p.isdigit() else getattr(owner, p)
             if hasattr(owner, "invalidate_packed"):
                 owner.invalidate_packed()
+            if "_mx8" in owner.__dict__:                 # a quantised feed-forward (ltxmi/ff_mx8.py): quantise again
+                owner.__dict__["_mx8"].cache.clear()
 
 
 def fuse_paths(model, adapter):

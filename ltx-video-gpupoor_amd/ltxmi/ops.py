@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from . import _lib, derived
+from . import _lib, _lib_mx, derived
 from ._lib import lib, check
 
 BF16 = torch.bfloat16
@@ -1066,5 +1066,92 @@ def embedding(ids, table, out=None):
     tok = _prof_begin(("embedding", flat.numel(), D))
     check(lib.ltxmi_embedding_bf16(_ptr(flat), _ptr(table), table.stride(0), vocab, _ptr(o2), ldo, flat.numel(), D, _stream()),
           "ltxmi_embedding_bf16")
+    _prof_end(tok)
+    return out
+
+
+# ---- MX-FP8 (include/ltxmi_mx.h, bound by ltxmi/_lib_mx.py): e4m3 elements, one E8M0 scale byte per 32 elements of a row
+E4M3 = torch.float8_e4m3fn
+
+
+def _chk_mx8(what, q, scales, K):
+    """q [rows, K] float8_e4m3fn (or uint8) and scales [rows, K / 32] uint8 on the device -> their 2-D row views."""
+    if q.dtype not in (E4M3, torch.uint8) or scales.dtype != torch.uint8 or not q.is_cuda or not scales.is_cuda:
+        raise TypeError(f"ltxmi.{what}: expected CUDA float8_e4m3fn elements and uint8 scales, got {q.dtype} / {scales.dtype} on "
+                        f"{q.device} / {scales.device}")
+    q2, rows, ldq = _rows(q)
+    s2, srows, lds = _rows(scales)
+    if q2.shape[1] != K or srows != rows or s2.shape[1] * 32 != K:
+        raise ValueError(f"ltxmi.{what}: elements {tuple(q.shape)} and scales {tuple(scales.shape)} do not belong to K={K}")
+    return q2, ldq, s2, lds, rows
+
+
+def quantize_mx8(x, out=None):
+    """x [..., K] bf16 (row-strided 2-D views are fine), K % 32 == 0 -> (q [..., K] float8_e4m3fn, scales [..., K / 32] uint8).
+    ``out``: a (q, scales) pair to write into."""
+    _chk_bf16(x)
+    x2, rows, ldx = _rows(x)
+    K = x2.shape[1]
+    if K % 32:
+        raise ValueError(f"ltxmi.quantize_mx8: K={K} must be a multiple of 32")
+    if out is None:
+        out = (torch.empty(x.shape, dtype=E4M3, device=x.device),
+               torch.empty((*x.shape[:-1], K // 32), dtype=torch.uint8, device=x.device))
+    q, scales = out
+    q2, ldq, s2, lds, orows = _chk_mx8("quantize_mx8", q, scales, K)
+    if orows != rows:
+        raise ValueError("ltxmi.quantize_mx8: out must have x's rows")
+    tok = _prof_begin(("quantize_mx8", rows, K))
+    check(_lib_mx.lib.ltxmi_quantize_mx8_bf16(_ptr(x2), ldx, _ptr(q2), ldq, _ptr(s2), lds, rows, K, _stream()), "ltxmi_quantize_mx8_bf16")
+    _prof_end(tok)
+    return q, scales
+
+
+def gemm_mx8(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
+             rows_per_group=1, mx_out=False):
+    """epi((a 2^a_scales)[M,K] @ (w 2^w_scales)[N,K]^T + bias) on the block-scaled MFMA; K % 128 == 0, N % 32 == 0.  The
+    keywords are ``gemm``'s.  ``mx_out=False``: a bf16 [M,N] (``out``: the tensor to write).  ``mx_out=True``: the result is
+    quantised from its fp32 value and returned as (q, scales) (``out``: such a pair); epilogue NONE or GELU_TANH."""
+    N, K = w.shape
+    a2, lda, as2, lda_s, M = _chk_mx8("gemm_mx8", a, a_scales, K)
+    w2, ldw, ws2, ldw_s, _ = _chk_mx8("gemm_mx8", w, w_scales, K)
+    _chk_bf16(bias, residual, gate_table, gate_temb)
+    args = _lib_mx.GemmMx8Args()
+    if mx_out:
+        if out is None:
+            out = (torch.empty((M, N), dtype=E4M3, device=a.device), torch.empty((M, N // 32), dtype=torch.uint8, device=a.device))
+        c2, ldcq, cs2, ldc_s, Mo = _chk_mx8("gemm_mx8", out[0], out[1], N)
+        if Mo != M:
+            raise ValueError("ltxmi.gemm_mx8: bad out shape")
+        args.Cq, args.ldcq, args.C_scales, args.ldc_s = c2.data_ptr(), ldcq, cs2.data_ptr(), ldc_s
+    else:
+        if out is None:
+            out = torch.empty((M, N), dtype=BF16, device=a.device)
+        _chk_bf16(out)
+        o2, Mo, ldc = _rows(out)
+        if Mo != M or o2.shape[1] != N:
+            raise ValueError("ltxmi.gemm_mx8: bad out shape")
+        args.C, args.ldc = o2.data_ptr(), ldc
+    args.Aq, args.lda, args.A_scales, args.lda_s = a2.data_ptr(), lda, as2.data_ptr(), lda_s
+    args.Wq, args.ldw, args.W_scales, args.ldw_s = w2.data_ptr(), ldw, ws2.data_ptr(), ldw_s
+    args.bias = bias.data_ptr() if bias is not None else None
+    args.M, args.N, args.K = M, N, K
+    args.epilogue = epilogue
+    if residual is not None:
+        r2, Mr, ldr = _rows(residual)
+        if Mr != M or r2.shape[1] != N:
+            raise ValueError(f"ltxmi.gemm_mx8: residual is [{Mr},{r2.shape[1]}], expected [{M},{N}]")
+        args.residual, args.ldr = r2.data_ptr(), ldr
+    if (gate_table is None) != (gate_temb is None):
+        raise ValueError("ltxmi.gemm_mx8: gate_table and gate_temb go together")
+    if gate_table is not None:
+        if gate_table.shape != (N,) or gate_temb.shape[-1] != N or gate_temb.stride(-1) != 1:
+            raise ValueError(f"ltxmi.gemm_mx8: gate_table must be [{N}] and gate_temb [groups, {N}] with a contiguous last dimension")
+        args.gate_table = gate_table.data_ptr()
+        args.gate_temb = gate_temb.data_ptr()
+        args.gate_ld = gate_temb.stride(0) if gate_temb.dim() == 2 else 0
+    args.rows_per_group = rows_per_group
+    tok = _prof_begin(("gemm_mx8", M, N, K, epilogue))
+    check(_lib_mx.lib.ltxmi_gemm_mx8(ctypes.byref(args), _stream()), "ltxmi_gemm_mx8")
     _prof_end(tok)
     return out

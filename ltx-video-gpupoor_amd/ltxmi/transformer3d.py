@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional
 import torch
 from torch import nn
 
-from . import lora, ops
+from . import ff_mx8, lora, ops
 from .attention import BasicTransformerBlock, SkipLayerStrategy
 from .derived import DerivedOwner, cache_key
 
@@ -153,6 +153,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         if any(k.startswith("model.diffusion_model.") for k in state_dict.keys()):
             state_dict = {k.replace("model.diffusion_model.", ""): v for k, v in state_dict.items()
                           if k.startswith("model.diffusion_model.")}
+        self._refuse_ff_freed("load_state_dict")
         st = lora.fused_state(self)
         if st is not None:
             if st.adapters and st.base:
@@ -172,6 +173,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
             raise ValueError("ltxmi: the adapter names linears outside the transformer blocks, which carry no adapter here: "
                              + ", ".join(other))
         lora.check_shapes(self, adapter, mine)
+        self._refuse_ff_quantized(mine.values(), "attach_lora")
         active = self.__dict__.setdefault("_lora_adapters", lora.OrderedDict())
         if name is None:
             name = f"lora{len(active)}"
@@ -222,6 +224,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         ``fuse_lora`` on the same linear merge from; ``keep_base=False`` merges in place and keeps nothing, and those three
         then raise for the linears concerned.  Fused and attached adapters may coexist: the attached ones run on top."""
         paths = lora.fuse_paths(self, adapter)
+        self._refuse_ff_quantized(paths, "fuse_lora")
         st = lora.fused_state(self)
         fused = st.adapters if st else {}
         if name is None:
@@ -260,6 +263,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
                 raise KeyError(f"ltxmi: no adapter named '{name}' is fused")
         paths = list(dict.fromkeys(p for name in weights for p in fused[name][2]))
         self._refuse_sealed(paths, "set_fused_lora_weights")
+        self._refuse_ff_quantized(paths, "set_fused_lora_weights", freed_only=True)
         for name, w in weights.items():
             fused[name][1] = float(w)
         lora.remerge(self, paths)
@@ -274,6 +278,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         names = list(fused) if name is None else [name]
         paths = list(dict.fromkeys(p for n in names for p in fused[n][2]))
         self._refuse_sealed(paths, "unfuse_lora")
+        self._refuse_ff_quantized(paths, "unfuse_lora", freed_only=True)
         for n in names:
             del fused[n]
         lora.remerge(self, paths)
@@ -286,12 +291,78 @@ class Transformer3DModel(DerivedOwner, nn.Module):
 
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)
+        if self._ff_freed():                     # the held MX-FP8 weights follow the device (never a dtype: they are e4m3 / E8M0)
+            dev = self.patchify_proj.weight.device
+            for b in self.transformer_blocks:
+                st = b.ff.__dict__["_mx8"]
+                st.sealed = tuple(tuple(t.to(dev) for t in pair) for pair in st.sealed)
         st = lora.fused_state(self)
         if st is not None:
             st.base = {path: fn(t) for path, t in st.base.items()}     # the base copies follow the weights (no parameters, no buffers)
         if self.__dict__.get("_lora_adapters"):
             lora.rebuild(self)                   # the per-linear state follows the weights' device
         return out
+
+    # ------------------------------------------------------------------ MX-FP8 feed-forward (ltxmi/ff_mx8.py)
+    FF_LINEARS = ("ff.net.0.proj", "ff.net.2")
+
+    def quantize_ff(self, keep_bf16: bool = True):
+        """Run the feed-forward pair of every block in MX-FP8 (e4m3 elements, one scale per 32 along K; the block-scaled MFMA):
+        quantise(norm) -> FF1 (GELU, written as MX-FP8) -> FF2 (gate + residual; a plain bf16 output on the fp32 stream).  The
+        weights are quantised from the bf16 tensors as they stand -- after ``fuse_lora``, the fused ones.  ``keep_bf16=True``: the
+        bf16 parameters stay, ``state_dict()`` is unchanged, an in-place edit of a weight quantises it again, ``unquantize_ff()``
+        gives the model back bit for bit.  ``keep_bf16=False``: the bf16 feed-forward weights are freed (5/8 of a block's linear
+        bytes become 5/16); ``unquantize_ff``, ``state_dict`` and ``load_state_dict`` then raise.  Adapters on the attention
+        linears are unaffected; one on a feed-forward linear has to be detached (or fused) first."""
+        if self.ff_quantized:
+            raise RuntimeError("ltxmi: quantize_ff(): the feed-forward is quantised already; unquantize_ff() first")
+        ffs = [b.ff for b in self.transformer_blocks]
+        for i, ff in enumerate(ffs):
+            ff_mx8.check(ff)
+            if lora.has_slot(ff, "ff1") or lora.has_slot(ff, "ff2"):
+                raise RuntimeError(f"ltxmi: quantize_ff(): an adapter is attached to transformer_blocks.{i}.ff; detach_lora() "
+                                   "first, or fuse_lora() it into the weights")
+        for ff in ffs:
+            ff.__dict__["_mx8"] = ff_mx8.FFState()
+        if not keep_bf16:
+            for ff in ffs:
+                st = ff.__dict__["_mx8"]
+                st.sealed = ff_mx8.weights(ff)
+                st.cache.clear()
+                for lin in (ff.net[0].proj, ff.net[2]):
+                    lin.weight.data = torch.empty(0, dtype=lin.weight.dtype, device=lin.weight.device)
+            st = lora.fused_state(self)
+            if st is not None:                       # base copies of freed weights are of no use any more
+                for path in [p for p in st.base if p.endswith(self.FF_LINEARS)]:
+                    del st.base[path]
+                    st.sealed.add(path)
+
+    def unquantize_ff(self):
+        """Back to the bf16 feed-forward: the model computes what it computed before ``quantize_ff``, bit for bit."""
+        self._refuse_ff_freed("unquantize_ff")
+        for b in self.transformer_blocks:
+            b.ff.__dict__.pop("_mx8", None)
+
+    @property
+    def ff_quantized(self) -> bool:
+        return any("_mx8" in b.ff.__dict__ for b in self.transformer_blocks)
+
+    def _ff_freed(self):
+        return any(b.ff.__dict__["_mx8"].sealed is not None for b in self.transformer_blocks if "_mx8" in b.ff.__dict__)
+
+    def _refuse_ff_freed(self, what):
+        if self._ff_freed():
+            raise RuntimeError(f"ltxmi: {what}(): quantize_ff(keep_bf16=False) freed the bf16 feed-forward weights; reload the "
+                               "checkpoint")
+
+    def _refuse_ff_quantized(self, paths, what, freed_only=False):
+        if (self._ff_freed() if freed_only else self.ff_quantized) and any(p.endswith(self.FF_LINEARS) for p in paths):
+            raise RuntimeError(f"ltxmi: {what}(): the feed-forward is quantised and the adapter names ff.net.0.proj / ff.net.2; "
+                               "unquantize_ff() first")
+
+    def state_dict(self, *args, **kwargs):
+        self._refuse_ff_freed("state_dict")
+        return super().state_dict(*args, **kwargs)
 
     # ------------------------------------------------------------------ helpers kept verbatim
     def create_skip_layer_mask(self, batch_size: int, num_conds: int, ptb_index: int,
