@@ -7,7 +7,7 @@ declaration on anything else -- nothing is guessed, and no unknown type turns in
   - ``typedef struct N { <type> a, b[DEFINE]; ... } N;`` with N in the caller's struct-name map;
   - ``<type> name(<type> [name], ...);``
 where <type> is int / int32_t (c_int32), int64_t, float, a pointer to one of those, to void or to uint32_t (c_void_p), a
-pointer to a struct declared above (POINTER(Struct)) and, as a return type, ``const char*`` (c_char_p).
+pointer to a struct declared above or handed in as known (POINTER(Struct)) and, as a return type, ``const char*`` (c_char_p).
 """
 import ctypes
 import re
@@ -30,9 +30,10 @@ class HeaderError(ValueError):
     pass
 
 
-def parse(text, struct_names):
-    """``text``: the header; ``struct_names``: C struct name -> Python class name, one entry per struct of the header."""
-    structs, by_c_name, constants, strings, signatures = {}, {}, {}, {}, {}
+def parse(text, struct_names, known_structs=None):
+    """``text``: the header; ``struct_names``: C struct name -> Python class name, one entry per struct of the header;
+    ``known_structs``: C struct name -> class, the structs of the headers this one includes that its prototypes may point to."""
+    structs, by_c_name, constants, strings, signatures = {}, dict(known_structs or {}), {}, {}, {}
 
     def ctype(base, star, decl, ret=False):
         if not star and base in SCALARS:

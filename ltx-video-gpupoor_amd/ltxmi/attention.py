@@ -26,7 +26,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from . import ff_mx8, lora, ops
+from . import attn_mx8, ff_mx8, lora, ops
 from .attention_seam import pay_attention
 from .derived import DerivedOwner, cache_key
 
@@ -201,6 +201,10 @@ class AttnProcessor2_0:
                  fused_residual=None, *args, **kwargs):
         hidden_states = hidden_states_wrapper[0]
         hidden_states_wrapper.clear()
+        mx = attn.__dict__.get("_mx8")      # Transformer3DModel.quantize_attention: this attention's linears in MX-FP8 (ltxmi/attn_mx8.py)
+        xq = None
+        if isinstance(hidden_states, tuple):                # (e4m3 [B, N, D], scales): ops.norm_modulate_mx8's output, attn1 only
+            xq, hidden_states = (hidden_states[0].reshape(-1, hidden_states[0].shape[-1]), hidden_states[1]), hidden_states[0]
         if hidden_states.dim() != 3:
             raise NotImplementedError("ltxmi.AttnProcessor2_0: only [B, N, D] inputs are on this path")
         B, N, _ = hidden_states.shape
@@ -211,9 +215,10 @@ class AttnProcessor2_0:
         is_cross = encoder_hidden_states is not None
         # only the pack this call uses is built: self-attention never materialises [to_k; to_v], cross-attention never
         # [to_q; to_k; to_v] (1.2 GB of HBM on the 2B model otherwise)
+        mx_proj, mx_out = mx is not None and mx.proj, mx is not None and mx.out
         if is_cross:
             wkv, bkv = attn.packed_kv()
-        else:
+        elif not mx_proj:
             wqkv, bqkv = attn.packed_qkv()
         if not isinstance(attn.q_norm, RMSNorm):
             raise NotImplementedError("ltxmi.AttnProcessor2_0: qk_norm=None is not on this path")
@@ -225,8 +230,11 @@ class AttnProcessor2_0:
             # its own: the only launch between the projection and attention is k's norm + RoPE.
             fuse_q = ops.attention_fuses_qnorm(B, H, N, N, dh) and D % 64 == 0 and attention_mask is None
             ss = torch.empty((B * N, D // 64), dtype=torch.float32, device=x2.device) if fuse_q else None
-            qkv = ops.gemm(x2, wqkv, bqkv, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0,
-                           **lora.pair(attn, "qkv", x2))                                    # [B*N, 3D]
+            if mx_proj:
+                qkv = attn_mx8.project(attn, xq if xq is not None else x2, ss, D if fuse_q else 0)
+            else:
+                qkv = ops.gemm(x2, wqkv, bqkv, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0,
+                               **lora.pair(attn, "qkv", x2))                                # [B*N, 3D]
             q2, k2, v2 = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
             cos = sin = None
             period = 0
@@ -261,8 +269,11 @@ class AttnProcessor2_0:
             # step, tools/bench_xattn_fuse.py).
             fuse_q = FUSE_CROSS_ATTENTION_Q and D % 64 == 0 and bool(ops.attention_fuses_qnorm(B, H, N, Lk, dh, attention_mask is not None))
             ss = torch.empty((B * N, D // 64), dtype=torch.float32, device=x2.device) if fuse_q else None
-            q2 = ops.gemm(x2, attn.to_q.weight, attn.to_q.bias, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0,
-                          **lora.pair(attn, "q", x2))                                      # [B*N, D]
+            if mx_proj:
+                q2 = attn_mx8.project(attn, x2, ss, D if fuse_q else 0)
+            else:
+                q2 = ops.gemm(x2, attn.to_q.weight, attn.to_q.bias, rowsumsq=ss, rowsumsq_cols=D if fuse_q else 0,
+                              **lora.pair(attn, "q", x2))                                  # [B*N, D]
             # The text keys/values depend on the prompt and this layer's weights only: within a generation
             # they are the same at every denoise step, so they are projected + normalised once and reused
             # (same kernels on the same inputs: identical values; the key and what it holds alive: ltxmi/derived.py).  An
@@ -326,6 +337,17 @@ class AttnProcessor2_0:
                 elif skip_layer_strategy == SkipLayerStrategy.AttentionSkip:
                     ops.stg_blend_(a3, hidden_states, m_dev)                        # :1127-1133
 
+        if mx_out:
+            # quantise(attention output, after the STG paths above) -> to_out.0 with the epilogue the bf16 call has
+            if fused_residual is not None:
+                residual, gate_table, gate_temb, rpg = fused_residual
+                r2 = residual.reshape(B * N, -1)
+                attn_mx8.to_out(attn, a3.reshape(B * N, D), out=r2, epilogue=ops.EPI_GATE_RESIDUAL, residual=r2,
+                                gate_table=gate_table, gate_temb=gate_temb, rows_per_group=rpg)
+                return residual
+            if attn.residual_connection or attn.rescale_output_factor != 1.0:
+                raise NotImplementedError("ltxmi.AttnProcessor2_0: residual_connection / rescale_output_factor")
+            return attn_mx8.to_out(attn, a3.reshape(B * N, D)).view(B, N, -1)
         w_o, b_o = attn.to_out[0].weight, attn.to_out[0].bias
         if fused_residual is not None:
             residual, gate_table, gate_temb, rpg = fused_residual
@@ -380,7 +402,11 @@ class BasicTransformerBlock(nn.Module):
     def prepare_shared_state(self):
         """Build, on the CURRENT stream, what the processors create lazily and cache for every later caller (the packed
         projection weights).  Called by the micro-batched block loop before its side streams fork."""
-        self.attn1.packed_qkv()
+        mx1 = self.attn1.__dict__.get("_mx8")
+        if mx1 is not None and mx1.proj:
+            attn_mx8.weights(self.attn1, "proj")
+        else:
+            self.attn1.packed_qkv()
         if self.attn2 is not None:
             self.attn2.packed_kv()
 
@@ -405,15 +431,27 @@ class BasicTransformerBlock(nn.Module):
         def chunk(i):                                     # (table row, temb column block) of ada value i
             return table[i], temb[:, i * D:(i + 1) * D]
 
+        mx1 = self.attn1.__dict__.get("_mx8")
+        if mx1 is not None or (self.attn2 is not None and "_mx8" in self.attn2.__dict__):
+            refuse = getattr(self.attn1.processor, "refuse_quantized_attention", None)
+            if refuse is not None:                                  # the sequence-parallel processors (ltxmi.distributed)
+                refuse()
+
         if hidden_states.dtype == torch.float32:
             return self._forward_stream32(hidden_states, chunk, rpg, freqs_cis, encoder_hidden_states,
                                           encoder_attention_mask, skip_layer_mask, host_mask, skip_layer_strategy)
 
         # 0/1. norm1 -> modulate(shift_msa=0, scale_msa=1) -> self-attention -> gate_msa(2) + residual
-        norm_h = torch.empty_like(hidden_states)
         sc_t, sc_e = chunk(1)
         sh_t, sh_e = chunk(0)
-        ops.norm_modulate(h2, norm_h.view(B * N, D), self.norm1.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
+        if mx1 is not None and mx1.proj and not (host_mask is not None and skip_layer_strategy == SkipLayerStrategy.AttentionSkip):
+            # the quantised projection's input straight from the norm: e4m3 + scales, no bf16 norm output (the AttentionSkip
+            # blend is the one reader of that output besides the projection; it takes the bf16 branch below)
+            nq, ns = ops.norm_modulate_mx8(h2, self.norm1.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
+            norm_h = (nq.view(B, N, D), ns)
+        else:
+            norm_h = torch.empty_like(hidden_states)
+            ops.norm_modulate(h2, norm_h.view(B * N, D), self.norm1.eps, self.norm_kind, sc_t, sc_e, sh_t, sh_e, rpg)
         g_t, g_e = chunk(2)
         self.attn1([norm_h], freqs_cis=freqs_cis, skip_layer_mask=skip_layer_mask,
                    skip_layer_strategy=skip_layer_strategy, fused_residual=(hidden_states, g_t, g_e, rpg))

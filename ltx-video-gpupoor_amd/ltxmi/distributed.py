@@ -194,6 +194,13 @@ def _refuse_fp32_stream(who):
                               "built for sequence parallelism; run it on one GPU or use the bf16 stream")
 
 
+def _refuse_quantized_attention(who):
+    """The MX-FP8 attention linears (``Transformer3DModel.quantize_attention``) are launches of ``AttnProcessor2_0`` alone: the
+    sharded projection, the K-blocked to_out operand and the exchange buffers here are bf16."""
+    raise NotImplementedError(f"ltxmi.distributed.{who}: quantize_attention() (the MX-FP8 attention linears) is not built for "
+                              "sequence parallelism; unquantize_attention() first, or run on one GPU")
+
+
 def _refuse_lora(owner, who):
     """Adapters (ltxmi/lora.py) are not carried through the exchanges: ``owner`` (an Attention, or the model) must hold none."""
     from . import lora
@@ -243,6 +250,11 @@ class UlyssesAttnProcessor:
     def refuse_fp32_stream(self):
         _refuse_fp32_stream("UlyssesAttnProcessor")
 
+    def refuse_quantized_attention(self):
+        """The hook ``BasicTransformerBlock.forward`` calls on ``attn1``'s processor, if it has one, when either attention of
+        the block is quantised; also called below for a quantised ``attn1`` this processor is handed directly."""
+        _refuse_quantized_attention("UlyssesAttnProcessor")
+
     def __call__(self, attn, hidden_states_wrapper, freqs_cis, encoder_hidden_states=None,
                  attention_mask=None, temb=None, skip_layer_mask=None, skip_layer_strategy=None,
                  fused_residual=None, *args, **kwargs):
@@ -252,6 +264,8 @@ class UlyssesAttnProcessor:
         hidden_states_wrapper.clear()
         assert encoder_hidden_states is None, "UlyssesAttnProcessor is for self-attention"
         _refuse_lora(attn, "UlyssesAttnProcessor")
+        if "_mx8" in attn.__dict__:
+            self.refuse_quantized_attention()
         if attention_mask is not None:
             raise NotImplementedError("UlyssesAttnProcessor: a self-attention mask is not on this path")
         P = self.simulate_world or dist.get_world_size(self.group)
@@ -320,8 +334,13 @@ class RingAttnProcessor(AttnProcessor2_0):
     def refuse_fp32_stream(self):
         _refuse_fp32_stream("RingAttnProcessor")
 
+    def refuse_quantized_attention(self):
+        _refuse_quantized_attention("RingAttnProcessor")
+
     def __call__(self, attn, *args, **kwargs):
         _refuse_lora(attn, "RingAttnProcessor")
+        if "_mx8" in attn.__dict__:
+            self.refuse_quantized_attention()
         return super().__call__(attn, *args, **kwargs)
 
     def attend(self, qkv_list, is_cross, **kw):
@@ -474,6 +493,8 @@ def usp_dit_forward(model, hidden_states, freqs_cis, encoder_hidden_states=None,
     if kw.get("mixed"):
         _refuse_fp32_stream("usp_dit_forward")
     _refuse_lora(model, "usp_dit_forward")
+    if getattr(model, "attention_quantized", False):
+        _refuse_quantized_attention("usp_dit_forward")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     N = hidden_states.shape[1]
     hs = shard_tokens(hidden_states, rank, world)

@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from . import _lib, _lib_mx, derived
+from . import _lib, _lib_mx, _lib_mxa, derived
 from ._lib import lib, check
 
 BF16 = torch.bfloat16
@@ -1108,10 +1108,12 @@ def quantize_mx8(x, out=None):
 
 
 def gemm_mx8(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
-             rows_per_group=1, mx_out=False):
+             rows_per_group=1, mx_out=False, rowsumsq=None, rowsumsq_cols=0):
     """epi((a 2^a_scales)[M,K] @ (w 2^w_scales)[N,K]^T + bias) on the block-scaled MFMA; K % 128 == 0, N % 32 == 0.  The
     keywords are ``gemm``'s.  ``mx_out=False``: a bf16 [M,N] (``out``: the tensor to write).  ``mx_out=True``: the result is
-    quantised from its fp32 value and returned as (q, scales) (``out``: such a pair); epilogue NONE or GELU_TANH."""
+    quantised from its fp32 value and returned as (q, scales) (``out``: such a pair); epilogue NONE or GELU_TANH.
+    ``rowsumsq`` (fp32 [M, >= rowsumsq_cols / 64], epilogue NONE, bf16 output): also receives the per-64-column sums of squares
+    of the bf16 outputs for the columns < rowsumsq_cols, as ``gemm``'s (include/ltxmi_mx_attn.h)."""
     N, K = w.shape
     a2, lda, as2, lda_s, M = _chk_mx8("gemm_mx8", a, a_scales, K)
     w2, ldw, ws2, ldw_s, _ = _chk_mx8("gemm_mx8", w, w_scales, K)
@@ -1151,7 +1153,40 @@ def gemm_mx8(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, r
         args.gate_temb = gate_temb.data_ptr()
         args.gate_ld = gate_temb.stride(0) if gate_temb.dim() == 2 else 0
     args.rows_per_group = rows_per_group
+    if rowsumsq is not None:
+        if rowsumsq.dtype != torch.float32 or not rowsumsq.is_cuda or rowsumsq.dim() != 2 or rowsumsq.shape[0] != M \
+                or rowsumsq.stride(1) != 1 or rowsumsq.shape[1] * 64 < rowsumsq_cols:
+            raise ValueError("ltxmi.gemm_mx8: rowsumsq must be a CUDA fp32 [M, >= rowsumsq_cols/64]")
     tok = _prof_begin(("gemm_mx8", M, N, K, epilogue))
-    check(_lib_mx.lib.ltxmi_gemm_mx8(ctypes.byref(args), _stream()), "ltxmi_gemm_mx8")
+    if rowsumsq is None:
+        check(_lib_mx.lib.ltxmi_gemm_mx8(ctypes.byref(args), _stream()), "ltxmi_gemm_mx8")
+    else:
+        check(_lib_mxa.lib.ltxmi_gemm_mx8_rowsumsq(ctypes.byref(args), _ptr(rowsumsq), rowsumsq_cols, rowsumsq.stride(0), _stream()),
+              "ltxmi_gemm_mx8_rowsumsq")
     _prof_end(tok)
     return out
+
+
+def norm_modulate_mx8(x, eps, kind, scale_table, scale_temb, shift_table, shift_temb, rows_per_group, out=None):
+    """``quantize_mx8(norm_modulate(x, ...))`` in one row pass, bit for bit, without the bf16 tensor in between: x [..., D] bf16,
+    D % 32 == 0 -> (q [..., D] float8_e4m3fn, scales [..., D / 32] uint8).  ``out``: a (q, scales) pair to write into."""
+    _chk_bf16(x, scale_table, scale_temb, shift_table, shift_temb)
+    x2, rows, ldx = _rows(x)
+    D = x2.shape[1]
+    if D % 32:
+        raise ValueError(f"ltxmi.norm_modulate_mx8: D={D} must be a multiple of 32")
+    if scale_temb.stride(0) != shift_temb.stride(0):
+        raise ValueError("ltxmi.norm_modulate_mx8: scale/shift tables must share a row stride")
+    if out is None:
+        out = (torch.empty(x.shape, dtype=E4M3, device=x.device),
+               torch.empty((*x.shape[:-1], D // 32), dtype=torch.uint8, device=x.device))
+    q, scales = out
+    q2, ldq, s2, lds, orows = _chk_mx8("norm_modulate_mx8", q, scales, D)
+    if orows != rows:
+        raise ValueError("ltxmi.norm_modulate_mx8: out must have x's rows")
+    tok = _prof_begin(("norm_modulate_mx8", rows, D))
+    check(_lib_mxa.lib.ltxmi_norm_modulate_mx8(_ptr(x2), ldx, _ptr(q2), ldq, _ptr(s2), lds, rows, D, eps, kind, _ptr(scale_table),
+                                               _ptr(scale_temb), _ptr(shift_table), _ptr(shift_temb), scale_temb.stride(0),
+                                               rows_per_group, _stream()), "ltxmi_norm_modulate_mx8")
+    _prof_end(tok)
+    return q, scales

@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional
 import torch
 from torch import nn
 
-from . import ff_mx8, lora, ops
+from . import attn_mx8, ff_mx8, lora, ops
 from .attention import BasicTransformerBlock, SkipLayerStrategy
 from .derived import DerivedOwner, cache_key
 
@@ -154,6 +154,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
             state_dict = {k.replace("model.diffusion_model.", ""): v for k, v in state_dict.items()
                           if k.startswith("model.diffusion_model.")}
         self._refuse_ff_freed("load_state_dict")
+        self._refuse_attn_freed("load_state_dict")
         st = lora.fused_state(self)
         if st is not None:
             if st.adapters and st.base:
@@ -174,6 +175,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
                              + ", ".join(other))
         lora.check_shapes(self, adapter, mine)
         self._refuse_ff_quantized(mine.values(), "attach_lora")
+        self._refuse_attn_quantized(mine.values(), "attach_lora")
         active = self.__dict__.setdefault("_lora_adapters", lora.OrderedDict())
         if name is None:
             name = f"lora{len(active)}"
@@ -225,6 +227,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         then raise for the linears concerned.  Fused and attached adapters may coexist: the attached ones run on top."""
         paths = lora.fuse_paths(self, adapter)
         self._refuse_ff_quantized(paths, "fuse_lora")
+        self._refuse_attn_quantized(paths, "fuse_lora")
         st = lora.fused_state(self)
         fused = st.adapters if st else {}
         if name is None:
@@ -264,6 +267,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         paths = list(dict.fromkeys(p for name in weights for p in fused[name][2]))
         self._refuse_sealed(paths, "set_fused_lora_weights")
         self._refuse_ff_quantized(paths, "set_fused_lora_weights", freed_only=True)
+        self._refuse_attn_quantized(paths, "set_fused_lora_weights", freed_only=True)
         for name, w in weights.items():
             fused[name][1] = float(w)
         lora.remerge(self, paths)
@@ -279,6 +283,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         paths = list(dict.fromkeys(p for n in names for p in fused[n][2]))
         self._refuse_sealed(paths, "unfuse_lora")
         self._refuse_ff_quantized(paths, "unfuse_lora", freed_only=True)
+        self._refuse_attn_quantized(paths, "unfuse_lora", freed_only=True)
         for n in names:
             del fused[n]
         lora.remerge(self, paths)
@@ -296,6 +301,11 @@ class Transformer3DModel(DerivedOwner, nn.Module):
             for b in self.transformer_blocks:
                 st = b.ff.__dict__["_mx8"]
                 st.sealed = tuple(tuple(t.to(dev) for t in pair) for pair in st.sealed)
+        for attn in self._quantized_attentions():    # the same for the attention linears held by quantize_attention(keep_bf16=False)
+            st = attn.__dict__["_mx8"]
+            if st.sealed is not None:
+                dev = self.patchify_proj.weight.device
+                st.sealed = {k: tuple(None if t is None else t.to(dev) for t in v) for k, v in st.sealed.items()}
         st = lora.fused_state(self)
         if st is not None:
             st.base = {path: fn(t) for path, t in st.base.items()}     # the base copies follow the weights (no parameters, no buffers)
@@ -360,8 +370,87 @@ class Transformer3DModel(DerivedOwner, nn.Module):
             raise RuntimeError(f"ltxmi: {what}(): the feed-forward is quantised and the adapter names ff.net.0.proj / ff.net.2; "
                                "unquantize_ff() first")
 
+    # ------------------------------------------------------------------ MX-FP8 attention linears (ltxmi/attn_mx8.py)
+    def quantize_attention(self, keep_bf16: bool = True, linears=None):
+        """Run the per-step attention linears of every block in MX-FP8, the second switch beside ``quantize_ff`` (they compose, in
+        either order).  ``linears``: a subset of ``attn_mx8.LINEARS`` = ("attn1.qkv", "attn1.to_out", "attn2.to_q",
+        "attn2.to_out"); None takes ``attn_mx8.DEFAULT_LINEARS``, the measured choice.  attn1.qkv takes its input quantised
+        straight from norm1 (``ops.norm_modulate_mx8``) and emits q's row sums; the to_out linears quantise the attention output
+        and keep their gate + residual epilogue; ``attn2.to_k`` / ``to_v`` (once per generation) stay bf16.  The weights are
+        quantised from the bf16 tensors as they stand -- after ``fuse_lora``, the fused ones.  ``keep_bf16`` as in
+        ``quantize_ff``: True keeps the parameters (``state_dict()`` unchanged, an in-place edit quantises again,
+        ``unquantize_attention()`` gives the model back bit for bit); False frees the bf16 weights of the chosen linears, and
+        ``unquantize_attention``, ``state_dict`` and ``load_state_dict`` then raise.  An adapter attached to a chosen linear has
+        to be detached (or fused) first; the sequence-parallel processors refuse a quantised attention."""
+        from .attention import AttnProcessor2_0
+        if self.attention_quantized:
+            raise RuntimeError("ltxmi: quantize_attention(): the attention is quantised already; unquantize_attention() first")
+        chosen = attn_mx8.resolve(linears)
+        plan = []                                    # (attention module, {"proj": bool, "out": bool})
+        for i, b in enumerate(self.transformer_blocks):
+            for owner in ("attn1", "attn2"):
+                attn = getattr(b, owner, None)
+                names = [n for n in chosen if attn_mx8.PARTS[n][0] == owner]
+                if attn is None or not names:
+                    continue
+                if type(attn.processor) is not AttnProcessor2_0:
+                    raise NotImplementedError(f"ltxmi: quantize_attention(): transformer_blocks.{i}.{owner} runs "
+                                              f"{type(attn.processor).__name__}; the MX-FP8 linears are AttnProcessor2_0's "
+                                              "(disable_sequence_parallel() first)")
+                for n in names:
+                    attn_mx8.check(attn, attn_mx8.PARTS[n][1], f"transformer_blocks.{i}.{n}")
+                    if lora.has_slot(attn, attn_mx8.LORA_SLOTS[n]):
+                        raise RuntimeError(f"ltxmi: quantize_attention(): an adapter is attached to transformer_blocks.{i}.{n}; "
+                                           "detach_lora() first, or fuse_lora() it into the weights")
+                which = {attn_mx8.PARTS[n][1] for n in names}
+                plan.append((attn, "proj" in which, "out" in which))
+        for attn, proj, out in plan:
+            attn.__dict__["_mx8"] = attn_mx8.AttnState(proj, out)
+        self.__dict__["_mx8_attn_linears"] = chosen
+        if not keep_bf16:
+            for attn, _, _ in plan:
+                attn_mx8.seal(attn)
+            st = lora.fused_state(self)
+            if st is not None:                       # base copies of freed weights are of no use any more
+                for path in [p for p in st.base if p.endswith(self._attn_lora_suffixes())]:
+                    del st.base[path]
+                    st.sealed.add(path)
+
+    def unquantize_attention(self):
+        """Back to the bf16 attention linears: the model computes what it computed before ``quantize_attention``, bit for bit."""
+        self._refuse_attn_freed("unquantize_attention")
+        for attn in self._quantized_attentions():
+            del attn.__dict__["_mx8"]
+        self.__dict__.pop("_mx8_attn_linears", None)
+
+    @property
+    def attention_quantized(self) -> bool:
+        return bool(self.__dict__.get("_mx8_attn_linears"))
+
+    def _quantized_attentions(self):
+        return [a for b in self.transformer_blocks for a in (b.attn1, getattr(b, "attn2", None))
+                if a is not None and "_mx8" in a.__dict__]
+
+    def _attn_lora_suffixes(self):
+        """The module-path endings by which an adapter names a quantised attention linear."""
+        return tuple(p for n in self.__dict__.get("_mx8_attn_linears", ()) for p in attn_mx8.PARTS[n][2])
+
+    def _attn_freed(self):
+        return any(a.__dict__["_mx8"].sealed is not None for a in self._quantized_attentions())
+
+    def _refuse_attn_freed(self, what):
+        if self._attn_freed():
+            raise RuntimeError(f"ltxmi: {what}(): quantize_attention(keep_bf16=False) freed the bf16 weights of the quantised "
+                               "attention linears; reload the checkpoint")
+
+    def _refuse_attn_quantized(self, paths, what, freed_only=False):
+        if (self._attn_freed() if freed_only else self.attention_quantized) and any(p.endswith(self._attn_lora_suffixes()) for p in paths):
+            raise RuntimeError(f"ltxmi: {what}(): the adapter names an attention linear that quantize_attention() runs in MX-FP8 ("
+                               + ", ".join(self.__dict__["_mx8_attn_linears"]) + "); unquantize_attention() first")
+
     def state_dict(self, *args, **kwargs):
         self._refuse_ff_freed("state_dict")
+        self._refuse_attn_freed("state_dict")
         return super().state_dict(*args, **kwargs)
 
     # ------------------------------------------------------------------ helpers kept verbatim
