@@ -228,7 +228,7 @@ def load_vae(path, device="cuda", dtype=torch.bfloat16, with_encoder=True):
 T5_PREFIXES = ("text_encoder.", "t5.", "model.")
 
 
-def load_t5_encoder(path_or_state_dict, config, device="cuda", dtype=torch.bfloat16):
+def load_t5_encoder(path_or_state_dict, config, device="cuda", dtype=torch.bfloat16, mx8=False):
     """``t5.T5EncoderModel`` from a safetensors file (or a state dict) and its config (a dict, or the path of a
     ``T5_config.json``): what ltxv.py:200-209 does with ``T5_xxl_1.1_enc_bf16.safetensors``.
 
@@ -238,7 +238,9 @@ def load_t5_encoder(path_or_state_dict, config, device="cuda", dtype=torch.bfloa
     of ``shared.weight``), with the prefixes ``text_encoder.``, ``t5.``, ``model.`` or none stripped.  Every encoder tensor
     must be there; keys that name nothing in the encoder (a full T5's ``decoder.*`` and ``lm_head.weight``) are skipped and
     returned as ``model.unexpected_keys``.  Tensors are cast to ``dtype`` and go straight to ``device``; the stacked ``[q; k; v]``
-    and ``[wi_0; wi_1]`` GEMM operands are built here, once, and the five weights are views of them (no second copy)."""
+    and ``[wi_0; wi_1]`` GEMM operands are built here, once, and the five weights are views of them (no second copy).
+    ``mx8=True``: the encoder is quantised after loading with ``quantize(keep_bf16=False)`` (the default set of linears; their
+    bf16 weights are freed)."""
     from .t5 import T5Config, T5EncoderModel
     if isinstance(config, (str, os.PathLike)):
         with open(config) as f:
@@ -275,4 +277,6 @@ def load_t5_encoder(path_or_state_dict, config, device="cuda", dtype=torch.bfloa
         block.layer[0].SelfAttention.share_packed()
         block.layer[1].DenseReluDense.share_packed()
     model.unexpected_keys = sorted(unexpected)
+    if mx8:
+        model.quantize(keep_bf16=False)
     return model.eval()

@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from . import _lib, _lib_mx, _lib_mxa, derived
+from . import _lib, _lib_mx, _lib_mxa, _lib_mxt, derived
 from ._lib import lib, check
 
 BF16 = torch.bfloat16
@@ -1190,3 +1190,100 @@ def norm_modulate_mx8(x, eps, kind, scale_table, scale_temb, shift_table, shift_
                                                rows_per_group, _stream()), "ltxmi_norm_modulate_mx8")
     _prof_end(tok)
     return q, scales
+
+
+# ---- the MX-FP8 T5 encoder (include/ltxmi_mx_t5.h, bound by ltxmi/_lib_mxt.py; ltxmi/t5_mx8.py)
+MXT_FORMS, MXT_STAGES, MXT_MAX_ROWS = _lib_mxt.FORMS, _lib_mxt.STAGES, _lib_mxt.MAX_ROWS
+
+
+def _gemm_mx8_skinny_args(a, a_scales, w, w_scales, bias, out, epilogue, residual):
+    """The ``ltxmi_gemm_mx8_args`` of a bf16-output call and the tensor it writes."""
+    N, K = w.shape
+    a2, lda, as2, lda_s, M = _chk_mx8("gemm_mx8_skinny", a, a_scales, K)
+    w2, ldw, ws2, ldw_s, _ = _chk_mx8("gemm_mx8_skinny", w, w_scales, K)
+    _chk_bf16(bias, residual)
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=a.device)
+    _chk_bf16(out)
+    o2, Mo, ldc = _rows(out)
+    if Mo != M or o2.shape[1] != N:
+        raise ValueError("ltxmi.gemm_mx8_skinny: bad out shape")
+    args = _lib_mx.GemmMx8Args()
+    args.C, args.ldc = o2.data_ptr(), ldc
+    args.Aq, args.lda, args.A_scales, args.lda_s = a2.data_ptr(), lda, as2.data_ptr(), lda_s
+    args.Wq, args.ldw, args.W_scales, args.ldw_s = w2.data_ptr(), ldw, ws2.data_ptr(), ldw_s
+    args.bias = bias.data_ptr() if bias is not None else None
+    args.M, args.N, args.K = M, N, K
+    args.epilogue = epilogue
+    args.rows_per_group = 1
+    if residual is not None:
+        r2, Mr, ldr = _rows(residual)
+        if Mr != M or r2.shape[1] != N:
+            raise ValueError(f"ltxmi.gemm_mx8_skinny: residual is [{Mr},{r2.shape[1]}], expected [{M},{N}]")
+        args.residual, args.ldr = r2.data_ptr(), ldr
+    return args, out
+
+
+def gemm_mx8_skinny(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, residual=None, form=0):
+    """``gemm_mx8`` for M <= MXT_MAX_ROWS rows, bf16 output, epilogue NONE or GATE_RESIDUAL without a gate (the residual may be
+    ``out``): small output tiles that each walk all of K through a ring of LDS stages, bit-identical to ``gemm_mx8``
+    (ltxmi_gemm_mx8_skinny).  ``form``: 0 chooses the tile form by shape, one of ``MXT_FORMS`` forces it."""
+    args, out = _gemm_mx8_skinny_args(a, a_scales, w, w_scales, bias, out, epilogue, residual)
+    tok = _prof_begin(("gemm_mx8_skinny", args.M, args.N, args.K, epilogue))
+    check(_lib_mxt.lib.ltxmi_gemm_mx8_skinny(ctypes.byref(args), form, _stream()), "ltxmi_gemm_mx8_skinny")
+    _prof_end(tok)
+    return out
+
+
+def gemm_mx8_skinny_form(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, residual=None, form=0):
+    """The tile form ``gemm_mx8_skinny`` would run for these arguments (the launch's own check and plan; nothing is launched)."""
+    args, _ = _gemm_mx8_skinny_args(a, a_scales, w, w_scales, bias, out, epilogue, residual)
+    chosen = _lib_mxt.lib.ltxmi_gemm_mx8_skinny_form(ctypes.byref(args), form)
+    check(min(chosen, 0), "ltxmi_gemm_mx8_skinny_form")
+    return chosen
+
+
+def _mx8_out(what, x, K, out):
+    """The (q, scales) pair a fused row pass writes for the rows of ``x`` and K output channels -> its row views."""
+    if out is None:
+        out = (torch.empty((*x.shape[:-1], K), dtype=E4M3, device=x.device),
+               torch.empty((*x.shape[:-1], K // 32), dtype=torch.uint8, device=x.device))
+    q2, ldq, s2, lds, orows = _chk_mx8(what, out[0], out[1], K)
+    return out, q2, ldq, s2, lds, orows
+
+
+def rmsnorm_weight_mx8(x, weight, eps, out=None):
+    """``quantize_mx8(rmsnorm_weight(x, weight, eps))`` in one row pass, bit for bit, without the bf16 tensor in between:
+    x [..., D] bf16, D % 32 == 0 -> (q [..., D] float8_e4m3fn, scales [..., D / 32] uint8).  ``out``: such a pair to write into."""
+    _chk_bf16(x, weight)
+    x2, rows, ldx = _rows(x)
+    D = x2.shape[1]
+    if D % 32:
+        raise ValueError(f"ltxmi.rmsnorm_weight_mx8: D={D} must be a multiple of 32")
+    if weight.shape != (D,) or weight.stride(0) != 1:
+        raise ValueError(f"ltxmi.rmsnorm_weight_mx8: weight must be a contiguous [{D}]")
+    out, q2, ldq, s2, lds, orows = _mx8_out("rmsnorm_weight_mx8", x, D, out)
+    if orows != rows:
+        raise ValueError("ltxmi.rmsnorm_weight_mx8: out must have x's rows")
+    tok = _prof_begin(("rmsnorm_weight_mx8", rows, D))
+    check(_lib_mxt.lib.ltxmi_rmsnorm_weight_mx8(_ptr(x2), ldx, _ptr(q2), ldq, _ptr(s2), lds, rows, D, _ptr(weight), float(eps),
+                                                _stream()), "ltxmi_rmsnorm_weight_mx8")
+    _prof_end(tok)
+    return out
+
+
+def gated_gelu_mx8(h, out=None):
+    """``quantize_mx8(gated_gelu(h))`` in one pass, bit for bit: h [rows, 2F] bf16, F % 32 == 0 -> (q [rows, F] float8_e4m3fn,
+    scales [rows, F / 32] uint8).  ``out``: such a pair to write into."""
+    _chk_bf16(h)
+    h2, rows, ldh = _rows(h)
+    if h2.shape[1] % 64:
+        raise ValueError(f"ltxmi.gated_gelu_mx8: h must be [rows, 2F] with F a multiple of 32, got {tuple(h.shape)}")
+    F = h2.shape[1] // 2
+    out, q2, ldq, s2, lds, orows = _mx8_out("gated_gelu_mx8", h, F, out)
+    if orows != rows:
+        raise ValueError("ltxmi.gated_gelu_mx8: out must have h's rows")
+    tok = _prof_begin(("gated_gelu_mx8", rows, F))
+    check(_lib_mxt.lib.ltxmi_gated_gelu_mx8(_ptr(h2), ldh, _ptr(q2), ldq, _ptr(s2), lds, rows, F, _stream()), "ltxmi_gated_gelu_mx8")
+    _prof_end(tok)
+    return out

@@ -13,6 +13,9 @@ pipe to the softmax (HF rounds q k^T, and again after adding the bias, to bf16),
 accumulator of the o / wo GEMM (HF rounds the linear's output, then the sum).  The norms and the gated activation round
 exactly where T5LayerNorm and T5DenseGatedActDense round.
 
+``T5EncoderModel.quantize()`` runs the four projections of every block in MX-FP8 (ltxmi/t5_mx8.py); a model that was never
+quantised makes exactly the launches above.
+
 The tokenizer (sentencepiece, on the CPU) stays the caller's."""
 import collections
 import math
@@ -20,7 +23,7 @@ import math
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, t5_mx8
 from .derived import DerivedOwner
 
 MAX_TOKENS = 512                     # ltxmi_attention_relbias_bf16: a query's score row is held in registers
@@ -148,6 +151,8 @@ class T5LayerSelfAttention(nn.Module):
         self.layer_norm = T5LayerNorm(cfg.d_model, cfg.layer_norm_epsilon)
 
     def forward(self, x, B, L, rel, key_bias):
+        if "_mx8" in self.SelfAttention.__dict__:                # T5EncoderModel.quantize(): ltxmi/t5_mx8.py
+            return t5_mx8.self_attention(self.SelfAttention, self.layer_norm, x, B, L, rel, key_bias)
         return self.SelfAttention(self.layer_norm(x), x, B, L, rel, key_bias)
 
 
@@ -173,6 +178,8 @@ class T5LayerFF(nn.Module):
         self.layer_norm = T5LayerNorm(cfg.d_model, cfg.layer_norm_epsilon)
 
     def forward(self, x):
+        if "_mx8" in self.DenseReluDense.__dict__:               # T5EncoderModel.quantize(): ltxmi/t5_mx8.py
+            return t5_mx8.feed_forward(self.DenseReluDense, self.layer_norm, x)
         return self.DenseReluDense(self.layer_norm(x), x)
 
 
@@ -221,11 +228,84 @@ class T5EncoderModel(DerivedOwner, nn.Module):
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         """HF's names; ``encoder.embed_tokens.weight`` (HF ties it to ``shared.weight`` and saves both) is an alias."""
+        self._refuse_freed("load_state_dict")
         sd = dict(state_dict)
         alias = sd.pop("encoder.embed_tokens.weight", None)
         if alias is not None:
             sd.setdefault("shared.weight", alias)
         return super().load_state_dict(sd, strict=strict, **kw)
+
+    def state_dict(self, *args, **kwargs):
+        self._refuse_freed("state_dict")
+        return super().state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        dev = self.shared.weight.device
+        for mod in self._quantized_modules():        # weights held by quantize(keep_bf16=False) follow the device (never a dtype)
+            st = mod.__dict__["_mx8"]
+            if st.sealed is not None:
+                st.sealed = {name: tuple(t.to(dev) for t in pair) for name, pair in st.sealed.items()}
+        return out
+
+    # ------------------------------------------------------------------ MX-FP8 projections (ltxmi/t5_mx8.py)
+    def _linear_owners(self):
+        for i, block in enumerate(self.encoder.block):
+            yield f"encoder.block.{i}.layer.0.SelfAttention", block.layer[0].SelfAttention, t5_mx8.ATTENTION_LINEARS
+            yield f"encoder.block.{i}.layer.1.DenseReluDense", block.layer[1].DenseReluDense, t5_mx8.FF_LINEARS
+
+    def _quantized_modules(self):
+        return [mod for _, mod, _ in self._linear_owners() if "_mx8" in mod.__dict__]
+
+    def quantize(self, keep_bf16: bool = True, linears=None):
+        """Run the projections of every block in MX-FP8 (e4m3 elements, one scale per 32 along K; the block-scaled MFMA) on the
+        small-M GEMM ``ops.gemm_mx8_skinny``.  ``linears``: a subset of ``t5_mx8.LINEARS`` = ("qkv", "o", "wi", "wo"); None takes
+        ``t5_mx8.DEFAULT_LINEARS``, the measured choice.  The weights are quantised from the bf16 tensors as they stand; the
+        embedding, the relative-bias table and the norm weights stay bf16.  ``keep_bf16=True``: the bf16 parameters stay,
+        ``state_dict()`` is unchanged, an in-place edit of a weight quantises it again, ``unquantize()`` gives the model back bit
+        for bit.  ``keep_bf16=False``: the bf16 weights of the chosen linears are freed; ``unquantize``, ``state_dict`` and
+        ``load_state_dict`` then raise."""
+        if self.quantized:
+            raise RuntimeError("ltxmi: T5EncoderModel.quantize(): the encoder is quantised already; unquantize() first")
+        chosen = t5_mx8.resolve(linears)
+        plan = []
+        for path, mod, names in self._linear_owners():
+            mine = [n for n in names if n in chosen]
+            for n in mine:
+                t5_mx8.check(mod, n, f"{path}.{n}")
+            if mine:
+                plan.append((mod, mine))
+        if not keep_bf16 and not self.shared.weight.is_cuda:
+            raise TypeError("ltxmi: T5EncoderModel.quantize(keep_bf16=False): the weights are quantised on the GPU; move the "
+                            f"encoder there first (it is on {self.shared.weight.device})")
+        for mod, mine in plan:
+            mod.__dict__["_mx8"] = t5_mx8.State(mine)
+        self.__dict__["_mx8_linears"] = chosen
+        if not keep_bf16:
+            for mod, _ in plan:
+                t5_mx8.seal(mod)
+        return self
+
+    def unquantize(self):
+        """Back to the bf16 projections: the encoder computes what it computed before ``quantize``, bit for bit."""
+        self._refuse_freed("unquantize")
+        for mod in self._quantized_modules():
+            del mod.__dict__["_mx8"]
+        self.__dict__.pop("_mx8_linears", None)
+        return self
+
+    @property
+    def quantized(self):
+        return bool(self.__dict__.get("_mx8_linears"))
+
+    @property
+    def quantized_linears(self):
+        return tuple(self.__dict__.get("_mx8_linears", ()))
+
+    def _refuse_freed(self, what):
+        if any(mod.__dict__["_mx8"].sealed is not None for mod in self._quantized_modules()):
+            raise RuntimeError(f"ltxmi: T5EncoderModel.{what}(): quantize(keep_bf16=False) freed the bf16 weights of the quantised "
+                               "linears (" + ", ".join(self.quantized_linears) + "); reload the encoder")
 
     def rel_bias(self, L):
         """Block 0's bias table expanded over the offsets of an L x L call, once per (L, weight version); every block reads it."""
