@@ -12,6 +12,8 @@ each product exact to 2^-24, summed in any order, are within 64 * 2^-24 = 3.8e-6
                     third tile holds 32 columns);
   (1, 288, 256)     M = 1.
 Each with and without a bias, over the operand families plain and row_scales.
+EXACT SUMS (``rss_exact``): mx8_cases' flat probe, whose outputs are small integers; the sums are then exact in fp32 in any order
+and must equal the float64 sums, with no tolerance, at the first block, a whole band of tiles and into the narrow last band.
 
 FUSED NORM + QUANTISE (ltxmi_norm_modulate_mx8).  "norm-modulate, round to bf16, quantise": ``norm_quant_restate`` is
 norm_cases.norm_modulate_op in float64, one rounding to bf16, mx8_cases.quantize.  On the device the entry must equal the two
@@ -32,6 +34,11 @@ RSS_FAMILIES = ["plain", "row_scales"]
 RSS_CASES = [dict(shape=s, cols=c, bias=b, family=f) for s, cc in RSS_SHAPES.items() for c in cc for b in (True, False)
              for f in RSS_FAMILIES]
 RSS_RTOL, RSS_ATOL = 1e-5, 1e-6
+# exact sums on mx8_cases' flat probe, one K-tile.  (300, 2336, 128) is 2 x 10 tiles in bands of 8: cols 64 is the first block,
+# 2048 the whole first band, 2304 reaches into the narrow band (the last, 32-column tile holds no block); (257, 64, 128) is 2 x 1
+# tiles, one row in the second
+RSS_EXACT_SHAPES = {(300, 2336, 128): (64, 2048, 2304), (257, 64, 128): (64,)}
+RSS_EXACT_CASES = [dict(shape=s, cols=c, bias=b) for s, cc in RSS_EXACT_SHAPES.items() for c in cc for b in (True, False)]
 
 NORM_ROWS, NORM_D, NORM_KINDS, NORM_RPG = (1, 37, 300), (64, 2048, 2080, 4096), ("rms", "layer"), (1, 13)
 NORM_CASES = [dict(rows=r, D=D, kind=k, rpg=g) for r in NORM_ROWS for D in NORM_D for k in NORM_KINDS for g in NORM_RPG]
@@ -58,6 +65,25 @@ def gemm_rowsumsq_restate(d, cols, bias=True):
     acc = mc.product(d, torch.float32)[0]
     c = (acc + d["bias"].to(torch.float32) if bias else acc).to(BF)
     return c, rowsumsq(c, cols)
+
+
+def rss_exact_id(c):
+    return "x".join(map(str, c["shape"])) + f"-cols{c['cols']}-{'bias' if c['bias'] else 'nobias'}"
+
+
+def rss_exact(c, device="cpu"):
+    """An RSS_EXACT_CASES entry -> mx8_cases.exact's dict (epilogue none, bf16 output) with ``sums`` float64 [M, cols / 64]: the
+    outputs are integers of magnitude <= 15 (<= 7 without the bias), so a block's sum is an integer <= 64 * 225 and every partial
+    sum in any order is exact in fp32: the device's sums must EQUAL these."""
+    d = mc.exact(dict(shape=c["shape"], epi="none", bias=c["bias"], out="bf16", in_place=False, rpg=None, one_hot="a"), device)
+    d["sums"] = rowsumsq(d["truth"].to(BF), c["cols"])
+    return d
+
+
+def rss_exact_ok(d):
+    t, s = d["truth"], d["sums"]
+    return mc.exact_ok(d) and bool((t == t.round()).all()) and float(t.abs().max()) <= 15 and float(s.max()) <= 64 * 225 and \
+        bool((s.to(torch.float32).to(F64) == s).all())
 
 
 # ------------------------------------------------------------------------------------------------- fused norm + quantise

@@ -6,8 +6,16 @@ pinned on the CPU by tests/test_mx8_cases.py).
   layout probe  the FIRST GEMM test: one-hot rows against asymmetric small integers with a different power-of-two scale in every
                 block and row on both sides.  Every output is one exactly representable product and must match bit for bit: a
                 swapped lane map, a scale from the wrong block or a permuted K fails on almost every element.  Both operands take
-                the one-hot role in turn (each checks the other's map);
-  witness       exact data that shows how the scaled MFMA sums (a cut at 2^-13 of the largest product inside a group of 8 k): the
+                the one-hot role in turn (each checks the other's map).  Shapes (mx8_cases.PROBE_SHAPES): 1, 2, 3, 4, 5 and 7
+                K-tiles -- every path of the prologue and the K loop -- and the grids 1 x 1, 2 x 1, 2 x 10 and 3 x 12 of the band
+                walk (a last band narrower than 8 tiles, a 32-column last tile, one valid row in a tile).  Variants: scale bytes
+                over 1 .. 253, and operands as strided views at 4-byte aligned scale addresses;
+  outputs       every GEMM test hands in its output inside a buffer of NaN patterns (mx8_cases.guarded): none may be left
+                inside the view, nothing outside it may change;
+  exact         the flat probe (integer outputs) under every epilogue that is exact on such data -- bias and no bias, residual
+                out of and in place, the gate with 1, 7 and M + 3 rows per group, the e4m3 pack and its scale -- with zero
+                tolerance; the fp32 scale rule exactly at, above and below its threshold 1.75 * 2^k;
+  witness      exact data that shows how the scaled MFMA sums (a cut at 2^-13 of the largest product inside a group of 8 k): the
                 reason for the TRUNC term below;
   random        plain / cancel / row_scales at (300, 288, 256) and (2048, 4096, 8192), M = 1, every epilogue: per element
                 2^-7 |truth| + SLACK mag + TRUNC tmag, plus the per-row and per-256-column figures of gemm_cases.compare (on the
@@ -94,13 +102,118 @@ def test_quantizer_is_bit_identical_to_the_restatement(rows, K, family):
 def test_layout_probe(shape, one_hot):
     from ltxmi import ops
     M, N, K = shape
-    aq, a_s, wq, w_s, want = mc.probe(M, N, K, one_hot)
-    out = ops.gemm_mx8(aq.to(DEV), a_s.to(DEV), wq.to(DEV), w_s.to(DEV))
+    aq, a_s, wq, w_s, want = mc.probe(M, N, K, one_hot, device=DEV)
+    _bf16_equals(lambda out: ops.gemm_mx8(aq, a_s, wq, w_s, out=out), want)
+
+
+def _bf16_equals(call, want, prepare=None):
+    """``call(out)`` on a guarded [M, N] bf16 view (``prepare(out)`` fills it first: an in-place residual): nothing outside the
+    view changed, no guard pattern is left inside it -- a tile never written fails here by itself -- and the view holds
+    ``want``'s bits.  -> the view."""
+    M, N = want.shape
+    buf, out = mc.guarded(M, N, 8, "bf16", DEV)
+    if prepare is not None:
+        prepare(out)
+    call(out)
     torch.cuda.synchronize()
-    got = out.cpu()
-    same = got.view(torch.int16) == want.view(torch.int16)
+    left, outside = mc.guard_figures(buf, out, "bf16")
+    assert outside == 0, f"{outside} elements outside the output view changed"
+    assert left == 0, f"{left} outputs were never written"
+    same = out.view(torch.int16) == want.to(DEV).view(torch.int16)
     assert bool(same.all()), (f"{int((~same).sum())} of {same.numel()} outputs differ; first at {(~same).nonzero()[0].tolist()}: "
-                              f"{float(got[tuple((~same).nonzero()[0])])} for {float(want[tuple((~same).nonzero()[0])])}")
+                              f"{float(out[tuple((~same).nonzero()[0])])} for {float(want[tuple((~same).nonzero()[0])])}")
+    return out
+
+
+@pytest.mark.parametrize("one_hot", ["a", "w"])
+@pytest.mark.parametrize("v", mc.PROBE_VARIANTS, ids=lambda v: "x".join(map(str, v["shape"])) + f"-{v['scales']}-{v['geometry']}")
+def test_layout_probe_variants(v, one_hot):
+    """Scale bytes over the whole E8M0 range, and operands handed over as views (lda > K, lda_s > K / 32 from a 4-byte aligned
+    address, the weight a row range of a taller matrix): the expected bits, and for the views also the contiguous call's."""
+    from ltxmi import ops
+    M, N, K = v["shape"]
+    aq, a_s, wq, w_s, want = mc.probe(M, N, K, one_hot, v["scales"], v["geometry"], device=DEV)
+    out = _bf16_equals(lambda out: ops.gemm_mx8(aq, a_s, wq, w_s, out=out), want)
+    if v["geometry"] == "strided":
+        assert aq.stride(0) == K + 16 and a_s.stride(0) == K // 32 + 4 and a_s.data_ptr() % 16 == 4 and wq.data_ptr() % 16 == 0
+        ref = ops.gemm_mx8(*(t.view(torch.uint8).contiguous() for t in (aq, a_s, wq, w_s)))
+        assert torch.equal(out.view(torch.int16), ref.view(torch.int16)), "the views and the contiguous operands give other bits"
+
+
+# ------------------------------------------------------------------------------------------------- exact epilogues
+def _exact_kw(c, d):
+    from ltxmi import ops
+    kw = dict(bias=d["bias"], epilogue=_epi(c["epi"]))
+    if c["epi"] == "gate":
+        kw.update(gate_table=d["gate_table"], gate_temb=d["gate_temb"], rows_per_group=d["rows_per_group"])
+    return kw
+
+
+@pytest.mark.parametrize("c", [c for c in mc.EXACT_CASES if c["out"] == "bf16"], ids=mc.exact_id)
+def test_exact_epilogues_bf16_output(c):
+    """Integer (and half-integer) data on which every fp32 operation of the epilogue is exact (mx8_cases.exact_ok): the bias and
+    its absence, the residual out of place and in place, the gate with groups of 1, 7 and all rows.  Zero tolerance."""
+    from ltxmi import ops
+    M, N, K = c["shape"]
+    d = mc.exact(c, device=DEV)
+    kw, prepare = _exact_kw(c, d), None
+    if c["epi"] in ("gate", "residual"):
+        if c["in_place"]:
+            prepare = lambda out: out.copy_(d["residual"])
+        else:                                       # a residual with a stride of its own
+            _, res = _strided(M, N, 16, mc.BF, 0.0)
+            res.copy_(d["residual"])
+            kw["residual"] = res
+
+    def call(out):
+        if c["in_place"]:
+            kw["residual"] = out
+        ops.gemm_mx8(d["aq"], d["a_scales"], d["wq"], d["w_scales"], out=out, **kw)
+    _bf16_equals(call, d["truth"].to(mc.BF), prepare)
+
+
+def _mx_equals(call, M, N, want_q, want_s):
+    """``call((q, scales))`` on guarded views: nothing outside them changed, no NaN byte is left inside, and the bytes EQUAL
+    the expected ones (no allowance near a threshold)."""
+    qbuf, qv = mc.guarded(M, N, 16, "e4m3", DEV)
+    sbuf, sv = mc.guarded(M, N // 32, 5, "scale", DEV)
+    call((qv, sv))
+    torch.cuda.synchronize()
+    for buf, view, kind in ((qbuf, qv, "e4m3"), (sbuf, sv, "scale")):
+        left, outside = mc.guard_figures(buf, view, kind)
+        assert outside == 0, f"{kind}: {outside} bytes outside the output view changed"
+        assert left == 0, f"{kind}: {left} bytes were never written"
+    bad = (sv != want_s.to(DEV)).nonzero()
+    assert bad.numel() == 0, ("scale bytes", bad[:4].tolist(), int(sv[tuple(bad[0])]), int(want_s[tuple(bad[0])]))
+    want = want_q.view(torch.uint8).to(DEV)
+    bad = (qv != want).nonzero()
+    assert bad.numel() == 0, ("elements", bad[:4].tolist(), int(qv[tuple(bad[0])]), int(want[tuple(bad[0])]))
+
+
+@pytest.mark.parametrize("c", [c for c in mc.EXACT_CASES if c["out"] == "mx"], ids=mc.exact_id)
+def test_exact_mx_output(c):
+    """Integers of magnitude <= 15: exact in e4m3 under the scale the rule picks, so the stored bytes are the restated quantiser's
+    on the float64 truth."""
+    from ltxmi import ops
+    M, N, K = c["shape"]
+    d = mc.exact(c, device=DEV)
+    want_s = mc.scale_bytes_real(d["truth"])
+    want_q = mc.quantize_elements(d["truth"], want_s)
+    _mx_equals(lambda out: ops.gemm_mx8(d["aq"], d["a_scales"], d["wq"], d["w_scales"], mx_out=True, out=out, **_exact_kw(c, d)),
+               M, N, want_q, want_s)
+
+
+def test_mx_output_scale_rule_at_its_threshold():
+    """fp32 accumulators exactly at, above and below 1.75 * 2^k (mx8_cases.witness_mx_out_threshold).  First the sums themselves:
+    the bf16-output call with a residual that cancels the large term returns the exact remainder -- if that fails, the hardware's
+    sum is what differs.  Then the MX-output bytes -- if those fail, the rule is."""
+    from ltxmi import ops
+    w = mc.witness_mx_out_threshold()
+    ops_in = [w[k].to(DEV) for k in ("aq", "a_scales", "wq", "w_scales")]
+    rows, N = w["residual"].shape
+    _bf16_equals(lambda out: ops.gemm_mx8(*ops_in, out=out, epilogue=ops.EPI_GATE_RESIDUAL, residual=w["residual"].to(DEV)),
+                 w["after"][:, None].expand(rows, N).to(mc.BF))
+    _mx_equals(lambda out: ops.gemm_mx8(*ops_in, mx_out=True, out=out), rows, N, w["q"], w["scales"])
 
 
 def test_scaled_mfma_truncation_witness():
@@ -149,7 +262,7 @@ def test_gemm_bf16_output(c):
     from ltxmi import ops
     M, N, K = c["shape"]
     d, truth, mag, tb = _inputs(c)
-    buf, out = _strided(M, N, 8, mc.BF, 7.0)
+    buf, out = mc.guarded(M, N, 8, "bf16", DEV)
     kw = _call(c, d, out=out)
     if c["epi"] == "gate":                      # in place, as the block's FF2 runs
         out.copy_(d["residual"])
@@ -160,7 +273,7 @@ def test_gemm_bf16_output(c):
         kw["residual"] = res
     ops.gemm_mx8(d["aq"], d["a_scales"], d["wq"], d["w_scales"], **kw)
     torch.cuda.synchronize()
-    assert _untouched(buf, out, 7.0), "wrote outside the output view"
+    assert mc.guard_figures(buf, out, "bf16") == (0, 0), "(outputs never written, elements changed outside the output view)"
     if c["family"] == "cancel" and c["epi"] in ("gate", "residual"):
         # Every output is the rounding residue of its own accumulator here: the truth is 2^-9 of the accumulator, and the
         # whole-tensor, per-row and per-block figures -- relative to the TRUTH's norm, with no magnitude term -- measure nothing but
@@ -184,11 +297,12 @@ def test_gemm_mx_output(c):
     from ltxmi import ops
     M, N, K = c["shape"]
     d, truth, mag, _ = _inputs(c)
-    qbuf, qv = _strided(M, N, 16, torch.uint8, SENTINEL)
-    sbuf, sv = _strided(M, N // 32, 5, torch.uint8, SENTINEL)
+    qbuf, qv = mc.guarded(M, N, 16, "e4m3", DEV)
+    sbuf, sv = mc.guarded(M, N // 32, 5, "scale", DEV)
     ops.gemm_mx8(d["aq"], d["a_scales"], d["wq"], d["w_scales"], mx_out=True, out=(qv, sv), **_call(c, d))
     torch.cuda.synchronize()
-    assert _untouched(qbuf, qv, SENTINEL) and _untouched(sbuf, sv, SENTINEL), "wrote outside the output views"
+    assert mc.guard_figures(qbuf, qv, "e4m3") == (0, 0) and mc.guard_figures(sbuf, sv, "scale") == (0, 0), \
+        "(bytes never written, bytes changed outside the output views)"
     assert bool((qv & 0x7f != 0x7f).all()), "a NaN element"
     f = mc.mx_out_figures(qv, sv, truth, mag)
     print(f"{mc.case_id(c)} mx-out: scale blocks outside the rule {f['scale_bad']}, worst value error {f['elem']:.3f} of its limit")

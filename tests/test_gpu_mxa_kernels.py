@@ -3,7 +3,9 @@ tests/test_mxa_cases.py).
 
   row sums    ltxmi_gemm_mx8_rowsumsq: C bit-equal to ops.gemm_mx8 on the same operands; the sums within rtol 1e-5 / atol 1e-6 of
               the float64 sums of squares of the STORED bf16 output; the -7.0 sentinels in the guard rows before and after, in the
-              blocks past ``cols`` and in the padding of a row stay intact; two runs give equal bits;
+              blocks past ``cols`` and in the padding of a row stay intact; two runs give equal bits.  On the flat probe's integer
+              outputs (mxa_cases.rss_exact) the sums EQUAL the float64 sums and C the truth, at the first block, a whole band
+              of tiles and into the narrow last band, inside NaN-filled buffers;
   fused norm  ltxmi_norm_modulate_mx8: (q, scales) bit-identical to ops.quantize_mx8(ops.norm_modulate(...)) with row-strided
               inputs and outputs and sentinels around them, and on mx8_cases' witness rows under a zero modulation."""
 import pytest
@@ -59,6 +61,33 @@ def test_gemm_rowsumsq(c):
     print(f"row sums: worst |got - want| - (atol + rtol |want|) = {float(err.max()):.3e}; "
           f"worst relative error {float(((got - want).abs() / want.abs().clamp_min(1e-30)).max()):.3e}")
     assert bool((err <= 0).all()), (err.argmax().item(), float(err.max()))
+
+
+@pytest.mark.parametrize("c", xc.RSS_EXACT_CASES, ids=xc.rss_exact_id)
+def test_gemm_rowsumsq_exact(c):
+    """The flat probe's integer outputs: C must equal the float64 truth and ops.gemm_mx8's C bit for bit, and the sums the
+    float64 sums with no tolerance.  C and the sums lie in buffers of NaN patterns: every output and every block below ``cols``
+    is written, the blocks at or past ``cols``, the row padding and the guard rows keep the pattern."""
+    from ltxmi import ops
+    M, N, K = c["shape"]
+    d = xc.rss_exact(c, device=DEV)
+    kw = dict(a=d["aq"], a_scales=d["a_scales"], w=d["wq"], w_scales=d["w_scales"], bias=d["bias"])
+    cols, nblk = c["cols"], (N + 63) // 64
+    cbuf, out = mc.guarded(M, N, 8, "bf16", DEV)
+    sbuf, sums = mc.guarded(M, nblk, 3, "f32", DEV)            # every block of N and a padding
+    ops.gemm_mx8(**kw, out=out, rowsumsq=sums, rowsumsq_cols=cols)
+    torch.cuda.synchronize()
+    assert mc.guard_figures(cbuf, out, "bf16") == (0, 0), "(outputs never written, elements changed outside the output view)"
+    want = d["truth"].to(mc.BF).to(DEV)
+    assert torch.equal(out.view(torch.int16), want.view(torch.int16)), "C differs from the truth"
+    assert torch.equal(out.view(torch.int16), ops.gemm_mx8(**kw).view(torch.int16)), "C differs from ops.gemm_mx8's"
+    written = sums[:, :cols // 64]
+    left, outside = mc.guard_figures(sbuf, written, "f32")
+    assert outside == 0, f"{outside} values at or past rowsumsq_cols, in the padding or in a guard row changed"
+    assert left == 0, f"{left} sums were never written"
+    got = written.double().cpu()
+    bad = (got != d["sums"]).nonzero()
+    assert bad.numel() == 0, (bad[:4].tolist(), float(got[tuple(bad[0])]), float(d["sums"][tuple(bad[0])]))
 
 
 def _strided(rows, cols, pad, dtype, fill):

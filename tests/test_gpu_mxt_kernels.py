@@ -5,7 +5,8 @@
                 {1, stages - 1, stages, 2 stages + 1} of the ring depth the header states, the families of tests/mx8_cases.py, the
                 epilogues none (with a bias, ldc > N) and residual (the residual IS the output, ldc > N); the guard rows and the
                 row padding of the output stay as they were.  The reference is computed once per (family, shape, epilogue) and
-                shared by the forms.  ``_form`` pins the form of every case first;
+                shared by the forms.  ``_form`` pins the form of every case first.  Every K-tile count used is one at which
+                tests/mx8_cases.py holds ops.gemm_mx8 itself to an independent truth (asserted);
   witnesses     mx8_cases.probe (one exactly representable product per output: the operand, scale and C/D lane maps) and
                 mx8_cases.witness_truncation (the hardware's own in-group cut) on every form, against the expected values
                 themselves, not against another kernel;
@@ -107,6 +108,13 @@ def test_the_k_tile_counts_cover_the_ring():
     from ltxmi import ops
     s = ops.MXT_STAGES
     assert _ktiles() == [1, s - 1, s, 2 * s + 1] and len(_ktiles()) == 4
+
+
+def test_every_k_tile_count_has_a_truth_behind_gemm_mx8():
+    """The skinny kernel is held to ops.gemm_mx8's bits; ops.gemm_mx8 is held to an independent truth at the K-tile counts of
+    mx8_cases.PROBE_SHAPES.  Every count used here must be among them, or the chain skinny -> gemm_mx8 -> truth is open."""
+    assert set(_ktiles()) <= set(mc.TRUTH_KTILES), (_ktiles(), mc.TRUTH_KTILES)
+    assert mc.TRUTH_KTILES == sorted({s[2] // 128 for s in mc.PROBE_SHAPES})
 
 
 @pytest.mark.parametrize("one_hot", ["a", "w"])

@@ -19,6 +19,30 @@ def test_case_tables():
     assert 37 % 13 and 300 % 13
 
 
+@pytest.mark.parametrize("c", xc.RSS_EXACT_CASES, ids=xc.rss_exact_id)
+def test_exact_row_sums_are_exact(c):
+    """The condition of the exact row sums: integer outputs of magnitude <= 15, sums that fp32 holds; and the shapes reach the
+    blocks their comments name."""
+    (M, N, K), cols = c["shape"], c["cols"]
+    assert K == 128 and N % 32 == 0 and cols % 64 == 0 and 0 < cols <= N
+    d = xc.rss_exact(c)
+    assert xc.rss_exact_ok(d)
+    assert d["sums"].shape == (M, cols // 64) and (d["bias"] is not None) == c["bias"]
+    assert float(d["truth"].abs().max()) == (15 if c["bias"] else 7)
+    # element by element, by hand
+    for m, b in ((0, 0), (M - 1, cols // 64 - 1)):
+        assert float(d["sums"][m, b]) == sum(int(v) ** 2 for v in d["truth"][m, 64 * b:64 * b + 64].tolist())
+    # no block sums to zero: a block the kernel left at zero cannot pass
+    assert float(d["sums"].min()) > 0
+
+
+def test_exact_row_sum_shapes():
+    assert set(xc.RSS_EXACT_SHAPES) == {(300, 2336, 128), (257, 64, 128)} and len(xc.RSS_EXACT_CASES) == 8
+    assert xc.RSS_EXACT_SHAPES[(300, 2336, 128)] == (64, 2048, 2304) and xc.RSS_EXACT_SHAPES[(257, 64, 128)] == (64,)
+    # 10 N-tiles in bands of 8: 2048 columns are the first band, 2304 end with the ninth tile, the tenth holds 32 columns
+    assert -(-2336 // 256) == 10 and 2048 == 8 * 256 and 2304 == 9 * 256 and 2336 - 2304 == 32
+
+
 @pytest.mark.parametrize("family", xc.RSS_FAMILIES)
 def test_row_sum_restatement(family):
     M, N, K = 300, 288, 256
