@@ -2,7 +2,8 @@
 // block-scaled MFMA of gfx950 (v_mfma_scale_f32_32x32x64_f8f6f4 with e4m3 operands: twice the bf16 rate per clock), fp32
 // accumulation.  The kernels' arguments, the tile constants and the checks of ltxmi_gemm_mx8_args are here; the kernel's
 // statements are gemm_mx8_kernel.inc, which gemm_mx8.hip includes into gemm_mx8_kernel<EPI, MXOUT> (include/ltxmi_mx.h) and
-// gemm_mx8_rss.hip into the row-sum kernel (include/ltxmi_mx_attn.h).
+// gemm_mx8_rss.hip into the row-sum kernel (include/ltxmi_mx_attn.h).  gemm_mx8_pair2.hip (include/ltxmi_mx_lora.h) restates the
+// K loop for two operand pairs and shares the epilogue's text, gemm_mx8_epilogue.inc.
 //
 // The tile kernel of gemm.hip carried over: 256 x 256 output tiles, 8 waves (2 x 4, 128 x 64 each), a K-tile of 128 e4m3 bytes
 // per row -- as many LDS bytes per row as that kernel's 64 bf16 -- so the LDS image (128-byte rows, 16-byte chunk c of row r at
@@ -115,6 +116,25 @@ static inline int mx8_check_args(const ltxmi_gemm_mx8_args* a, const char* what,
     p.tiles_m = (a->M + MX_BM - 1) / MX_BM;
     p.tiles_n = (a->N + MX_BN - 1) / MX_BN;
     LTXMI_REQUIRE((int64_t)p.tiles_m * p.tiles_n < (1ll << 31), LTXMI_ERR_UNSUPPORTED, "%s: too many tiles", what);
+    return LTXMI_OK;
+}
+
+// ---- host: the checks of the row sums of squares (include/ltxmi_mx_attn.h) for a struct mx8_check_args has passed; fills p's
+// three fields
+static inline int mx8_check_rss(const ltxmi_gemm_mx8_args* a, float* rowsumsq, int32_t rowsumsq_cols, int64_t rowsumsq_ld,
+                                const char* what, Mx8RssParams& p) {
+    LTXMI_REQUIRE(rowsumsq, LTXMI_ERR_INVALID_ARG, "%s: NULL rowsumsq", what);
+    LTXMI_REQUIRE(a->epilogue == LTXMI_EPI_NONE && !a->Cq, LTXMI_ERR_INVALID_ARG,
+                  "%s: the row sums go with epilogue NONE and a bf16 C (epilogue %d%s)", what, a->epilogue, a->Cq ? ", Cq set" : "");
+    LTXMI_REQUIRE(rowsumsq_cols > 0 && rowsumsq_cols % 64 == 0 && rowsumsq_cols <= a->N, LTXMI_ERR_INVALID_ARG,
+                  "%s: rowsumsq_cols=%d must be a positive multiple of 64 and <= N=%d", what, rowsumsq_cols, a->N);
+    LTXMI_REQUIRE(rowsumsq_ld >= rowsumsq_cols / 64, LTXMI_ERR_INVALID_ARG, "%s: rowsumsq_ld=%lld is shorter than rowsumsq_cols / 64 = %d",
+                  what, (long long)rowsumsq_ld, rowsumsq_cols / 64);
+    LTXMI_REQUIRE((((uintptr_t)rowsumsq) & 3) == 0, LTXMI_ERR_UNSUPPORTED, "%s: rowsumsq must be 4-byte aligned", what);
+    // a masked lane stores at 0xfffffff0, which has to lie outside the descriptor (above)
+    LTXMI_REQUIRE((int64_t)a->M * rowsumsq_ld * 4 < (1ll << 32) - 256, LTXMI_ERR_UNSUPPORTED,
+                  "%s: rowsumsq must span less than 2^32 - 256 bytes", what);
+    p.rss = rowsumsq; p.rss_ld = rowsumsq_ld; p.rss_cols = rowsumsq_cols;
     return LTXMI_OK;
 }
 

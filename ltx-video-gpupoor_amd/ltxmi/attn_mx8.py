@@ -16,7 +16,7 @@ so an in-place edit (a fused-LoRA re-merge, ``copy_``) quantises again on the ne
 weights are held here (``sealed``) and the bf16 weights of the chosen linears are freed; the biases stay."""
 import torch
 
-from . import derived, ops
+from . import derived, lora, ops
 
 LINEARS = ("attn1.qkv", "attn1.to_out", "attn2.to_q", "attn2.to_out")
 # The default of ``quantize_attention(linears=None)``: the linears whose quantised form, the quantiser pass it needs included,
@@ -106,10 +106,12 @@ def project(attn, x, rowsumsq=None, rowsumsq_cols=0):
     ``ops.norm_modulate_mx8`` -> bf16 [rows, N], with q's row sums of squares where asked for."""
     wq, ws, bias = weights(attn, "proj")
     xq = x if isinstance(x, tuple) else ops.quantize_mx8(x)
-    return ops.gemm_mx8(*xq, wq, ws, bias=bias, rowsumsq=rowsumsq, rowsumsq_cols=rowsumsq_cols)
+    return ops.gemm_mx8(*xq, wq, ws, bias=bias, rowsumsq=rowsumsq, rowsumsq_cols=rowsumsq_cols,
+                        **lora.pair_mx8(attn, "q" if attn.is_cross_attention else "qkv", xq))
 
 
 def to_out(attn, a2, **kw):
     """quantise(attention output) -> to_out.0; the keywords are ``ops.gemm_mx8``'s (the gate + residual epilogue, ``out``)."""
     wq, ws, bias = weights(attn, "out")
-    return ops.gemm_mx8(*ops.quantize_mx8(a2), wq, ws, bias=bias, **kw)
+    xq = ops.quantize_mx8(a2)
+    return ops.gemm_mx8(*xq, wq, ws, bias=bias, **lora.pair_mx8(attn, "out", xq), **kw)

@@ -8,7 +8,7 @@ quantises again on the next forward and ``.to()`` is followed.  ``keep_bf16=Fals
 (``sealed``) and the bf16 weights are freed; the biases stay."""
 import torch
 
-from . import derived, ops
+from . import derived, lora, ops
 
 
 class FFState:
@@ -46,9 +46,10 @@ def ff1(ff, norm_h2):
     """quantise(norm_h) -> FF1 with GELU, written as MX-FP8: (q, scales) of [rows, inner]; never bf16."""
     (w1q, w1s), _ = weights(ff)
     xq = ops.quantize_mx8(norm_h2)
-    return ops.gemm_mx8(*xq, w1q, w1s, bias=ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH, mx_out=True)
+    return ops.gemm_mx8(*xq, w1q, w1s, bias=ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH, mx_out=True,
+                        **lora.pair_mx8(ff, "ff1", xq))
 
 
 def ff2(ff, h, **kw):
     _, (w2q, w2s) = weights(ff)
-    return ops.gemm_mx8(*h, w2q, w2s, bias=ff.net[2].bias, **kw)
+    return ops.gemm_mx8(*h, w2q, w2s, bias=ff.net[2].bias, **lora.pair_mx8(ff, "ff2", h), **kw)

@@ -14,6 +14,11 @@ columns [g R, (g + 1) R) of T (``a2_group_cols = D``); a member without an adapt
 State per linear (``LoraSlot``) is rebuilt on attach / detach / weight change, cost O(adapter); with no adapter attached no
 slot exists and every call the package makes is the one it makes without this module.
 
+A linear that ``quantize_ff`` / ``quantize_attention`` run in MX-FP8 takes its adapters (``attach_lora(..., mx8=True)``) in MX-FP8
+too: a ``LoraSlotMx8`` holds the same stacked operands quantised once, r padded to 128, and the call site's ``pair_mx8`` makes
+``T = MX(xq . down_q^T)`` and hands the quantised ups to ``ops.gemm_mx8`` (ltxmi_gemm_mx8_pair2), which continues the linear's K
+loop with them.  Which form a slot has follows the linear's state at ``rebuild``.
+
 The other way to run an adapter, for strengths that stay fixed over a generation, is to FUSE it into the weights
 (``Transformer3DModel.fuse_lora``; the second half of this file): one launch of the GEMM per linear, exact and reversible, after
 which the model runs the kernels of a model without adapters."""
@@ -25,6 +30,7 @@ from . import ops
 
 BF16 = torch.bfloat16
 RANK_PAD = 64          # include/ltxmi.h: K2 of ltxmi_gemm_pair is a multiple of 64
+MX_RANK_PAD = 128      # include/ltxmi_mx_lora.h: K2 of ltxmi_gemm_mx8_pair is a multiple of 128 (a K-tile of the MX-FP8 GEMM)
 
 # the ten linears of a BasicTransformerBlock, by their path below ``transformer_blocks.<i>.``
 BLOCK_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v",
@@ -65,6 +71,55 @@ def pair(owner, slot, x2):
     if s is None:
         return {}
     return dict(a2=ops.gemm(x2, s.down), w2=s.up, a2_group_cols=s.group_cols)
+
+
+class LoraSlotMx8:
+    """The slot of a linear that runs in MX-FP8 (``attach_lora(mx8=True)``): down [G R, K] and up [N, R] quantised once, each as
+    (e4m3, scales) with R a multiple of 128, and the group width (0: one group) of one ``ops.gemm_mx8`` call."""
+    __slots__ = ("down", "up", "group_cols")
+
+    def __init__(self, down, up, group_cols):
+        self.down, self.up, self.group_cols = down, up, group_cols
+
+
+def pair_mx8(owner, slot, xq):
+    """``pair`` for a call site of ``ops.gemm_mx8``, whose input ``xq`` is an (e4m3, scales) pair: {} without an adapter on that
+    linear, else ``T = MX(xq . down_q^T)`` -- quantised straight from the fp32 accumulator -- and the quantised scaled ups
+    (include/ltxmi_mx_lora.h)."""
+    slots = owner.__dict__.get("_lora")
+    s = slots.get(slot) if slots else None
+    if s is None:
+        return {}
+    return dict(a2=ops.gemm_mx8(*xq, *s.down, mx_out=True), w2=s.up, a2_group_cols=s.group_cols)
+
+
+def runs_mx8(owner, slot):
+    """Whether the linear(s) of ``slot`` run in MX-FP8 (ltxmi/ff_mx8.py, ltxmi/attn_mx8.py): their adapters are then MX-FP8 pairs."""
+    st = owner.__dict__.get("_mx8")
+    if st is None or slot == "kv":
+        return False
+    if slot in ("ff1", "ff2"):
+        return True
+    return bool(st.out if slot == "out" else st.proj)
+
+
+def _held(owner, slot):
+    """The quantised weight a ``keep_bf16=False`` model holds for ``slot``, or None."""
+    st = owner.__dict__.get("_mx8")
+    if st is None or st.sealed is None or not runs_mx8(owner, slot):
+        return None
+    if slot in ("ff1", "ff2"):
+        return st.sealed[0 if slot == "ff1" else 1][0]
+    return st.sealed["out" if slot == "out" else "proj"][0]
+
+
+def member_shapes(owner, slot, members):
+    """[(out_features, in_features)] of the member linears of a slot; where ``quantize_*(keep_bf16=False)`` freed the bf16
+    weights, from the held quantised operand (the members of a packed projection are equal parts of it)."""
+    held = _held(owner, slot)
+    if held is None:
+        return [tuple(_get(owner, m).weight.shape) for m in members]
+    return [(held.shape[0] // len(members), held.shape[1])] * len(members)
 
 
 def has_slot(owner, slot):
@@ -126,11 +181,13 @@ def check_shapes(model, adapter, mine):
         owner = getattr(block, target.split(".")[0], None)
         if owner is None:
             raise KeyError(f"ltxmi.lora: '{path}' names no linear of this model")
-        lin = _get(block, target)
+        _get(block, target)
+        owner_name, slot, members = next(s for s in SLOTS if target in [f"{s[0]}.{m}" for m in s[2]])
+        shape = member_shapes(owner, slot, members)[[f"{owner_name}.{m}" for m in members].index(target)]
         down, up, _ = adapter.modules[path]
-        if down.shape[1] != lin.weight.shape[1] or up.shape[0] != lin.weight.shape[0]:
+        if down.shape[1] != shape[1] or up.shape[0] != shape[0]:
             raise ValueError(f"ltxmi.lora: '{path}' is [{up.shape[0]}, r] x [r, {down.shape[1]}] but the linear is "
-                             f"{tuple(lin.weight.shape)}")
+                             f"{tuple(shape)}")
 
 
 def rebuild(model):
@@ -158,23 +215,29 @@ def rebuild(model):
                     states.append(_member_state(_get(owner, m), entries) if entries else None)
                 if all(s is None for s in states):
                     continue
+                mx = runs_mx8(owner, slot)
+                pad, group_mult = (MX_RANK_PAD, 256) if mx else (RANK_PAD, 128)
                 R = max(s[0].shape[0] for s in states if s is not None)
-                R = (R + RANK_PAD - 1) // RANK_PAD * RANK_PAD
+                R = (R + pad - 1) // pad * pad
                 lins = [_get(owner, m) for m in members]
-                if len(members) > 1 and any(l.weight.shape[0] % 128 for l in lins):
+                shapes = member_shapes(owner, slot, members)
+                if len(members) > 1 and any(n % group_mult for n, _ in shapes):
                     raise NotImplementedError("ltxmi.lora: a packed projection takes an adapter only with an inner dimension "
-                                              "that is a multiple of 128")
+                                              f"that is a multiple of {group_mult}")
                 downs, ups = [], []
-                for lin, s in zip(lins, states):
-                    n, k = lin.weight.shape
+                for lin, (n, k), s in zip(lins, shapes, states):
                     if s is None:
                         downs.append(torch.zeros((R, k), dtype=BF16, device=lin.weight.device))
                         ups.append(torch.zeros((n, R), dtype=BF16, device=lin.weight.device))
                     else:
                         downs.append(_pad_to(s[0], rows=R))
                         ups.append(_pad_to(s[1], cols=R))
-                slots[slot] = LoraSlot(torch.cat(downs, 0).contiguous(), torch.cat(ups, 0).contiguous(),
-                                       lins[0].weight.shape[0] if len(members) > 1 else 0)
+                down, up = torch.cat(downs, 0).contiguous(), torch.cat(ups, 0).contiguous()
+                group_cols = shapes[0][0] if len(members) > 1 else 0
+                if mx:          # the stacked, padded operands quantised as one; zero blocks become scale byte 0, elements 0
+                    slots[slot] = LoraSlotMx8(ops.quantize_mx8(down), ops.quantize_mx8(up), group_cols)
+                else:
+                    slots[slot] = LoraSlot(down, up, group_cols)
             for owner, slots in owners.values():
                 owner.__dict__["_lora"] = slots or None
                 owner.__dict__["_lora_epoch"] = ep

@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from . import _lib, _lib_mx, _lib_mxa, _lib_mxt, derived
+from . import _lib, _lib_mx, _lib_mxa, _lib_mxl, _lib_mxt, derived
 from ._lib import lib, check
 
 BF16 = torch.bfloat16
@@ -1107,16 +1107,41 @@ def quantize_mx8(x, out=None):
     return q, scales
 
 
+def _gemm_mx8_pair(a, N, a2, w2, a2_group_cols):
+    """The ltxmi_gemm_mx8_pair of a second operand pair, or None without one: a2 = (q [M, groups * K2], scales) (row-strided views
+    are fine), w2 = (q [N, K2], scales)."""
+    if a2 is None and w2 is None:
+        return None
+    if a2 is None or w2 is None:
+        raise ValueError("ltxmi.gemm_mx8: a2 and w2 go together")
+    K2 = w2[0].shape[-1]
+    if a2_group_cols < 0 or (a2_group_cols > 0 and N % a2_group_cols):
+        raise ValueError(f"ltxmi.gemm_mx8: a2_group_cols={a2_group_cols} must be 0 or divide N={N}")
+    groups = N // a2_group_cols if a2_group_cols > 0 else 1
+    t2, lda2, ts2, lda2_s, M2 = _chk_mx8("gemm_mx8", a2[0], a2[1], groups * K2)
+    u2, ldw2, us2, ldw2_s, N2 = _chk_mx8("gemm_mx8", w2[0], w2[1], K2)
+    if M2 != _rows(a)[1] or N2 != N:
+        raise ValueError(f"ltxmi.gemm_mx8: a2 has {M2} rows, w2 has {N2}: expected {_rows(a)[1]}, {N}")
+    pair = _lib_mxl.GemmMx8Pair()
+    pair.A2q, pair.lda2, pair.A2_scales, pair.lda2_s = t2.data_ptr(), lda2, ts2.data_ptr(), lda2_s
+    pair.W2q, pair.ldw2, pair.W2_scales, pair.ldw2_s = u2.data_ptr(), ldw2, us2.data_ptr(), ldw2_s
+    pair.K2, pair.group_cols = K2, a2_group_cols
+    return pair
+
+
 def gemm_mx8(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, residual=None, gate_table=None, gate_temb=None,
-             rows_per_group=1, mx_out=False, rowsumsq=None, rowsumsq_cols=0):
+             rows_per_group=1, mx_out=False, rowsumsq=None, rowsumsq_cols=0, a2=None, w2=None, a2_group_cols=0):
     """epi((a 2^a_scales)[M,K] @ (w 2^w_scales)[N,K]^T + bias) on the block-scaled MFMA; K % 128 == 0, N % 32 == 0.  The
     keywords are ``gemm``'s.  ``mx_out=False``: a bf16 [M,N] (``out``: the tensor to write).  ``mx_out=True``: the result is
     quantised from its fp32 value and returned as (q, scales) (``out``: such a pair); epilogue NONE or GELU_TANH.
     ``rowsumsq`` (fp32 [M, >= rowsumsq_cols / 64], epilogue NONE, bf16 output): also receives the per-64-column sums of squares
-    of the bf16 outputs for the columns < rowsumsq_cols, as ``gemm``'s (include/ltxmi_mx_attn.h)."""
+    of the bf16 outputs for the columns < rowsumsq_cols, as ``gemm``'s (include/ltxmi_mx_attn.h).
+    ``a2`` = (q [M, groups * K2], scales), ``w2`` = (q [N, K2], scales): a second MX-FP8 operand pair accumulated behind the
+    first, ``gemm``'s ``a2`` / ``w2`` / ``a2_group_cols`` in MX-FP8 (include/ltxmi_mx_lora.h); K2 % 128 == 0."""
     N, K = w.shape
-    a2, lda, as2, lda_s, M = _chk_mx8("gemm_mx8", a, a_scales, K)
-    w2, ldw, ws2, ldw_s, _ = _chk_mx8("gemm_mx8", w, w_scales, K)
+    pair = _gemm_mx8_pair(a, N, a2, w2, a2_group_cols)
+    aq, lda, aqs, lda_s, M = _chk_mx8("gemm_mx8", a, a_scales, K)
+    wq, ldw, wqs, ldw_s, _ = _chk_mx8("gemm_mx8", w, w_scales, K)
     _chk_bf16(bias, residual, gate_table, gate_temb)
     args = _lib_mx.GemmMx8Args()
     if mx_out:
@@ -1134,8 +1159,8 @@ def gemm_mx8(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, r
         if Mo != M or o2.shape[1] != N:
             raise ValueError("ltxmi.gemm_mx8: bad out shape")
         args.C, args.ldc = o2.data_ptr(), ldc
-    args.Aq, args.lda, args.A_scales, args.lda_s = a2.data_ptr(), lda, as2.data_ptr(), lda_s
-    args.Wq, args.ldw, args.W_scales, args.ldw_s = w2.data_ptr(), ldw, ws2.data_ptr(), ldw_s
+    args.Aq, args.lda, args.A_scales, args.lda_s = aq.data_ptr(), lda, aqs.data_ptr(), lda_s
+    args.Wq, args.ldw, args.W_scales, args.ldw_s = wq.data_ptr(), ldw, wqs.data_ptr(), ldw_s
     args.bias = bias.data_ptr() if bias is not None else None
     args.M, args.N, args.K = M, N, K
     args.epilogue = epilogue
@@ -1158,7 +1183,10 @@ def gemm_mx8(a, a_scales, w, w_scales, bias=None, out=None, epilogue=EPI_NONE, r
                 or rowsumsq.stride(1) != 1 or rowsumsq.shape[1] * 64 < rowsumsq_cols:
             raise ValueError("ltxmi.gemm_mx8: rowsumsq must be a CUDA fp32 [M, >= rowsumsq_cols/64]")
     tok = _prof_begin(("gemm_mx8", M, N, K, epilogue))
-    if rowsumsq is None:
+    if pair is not None:
+        rss = (None, 0, 0) if rowsumsq is None else (_ptr(rowsumsq), rowsumsq_cols, rowsumsq.stride(0))
+        check(_lib_mxl.lib.ltxmi_gemm_mx8_pair2(ctypes.byref(args), ctypes.byref(pair), *rss, _stream()), "ltxmi_gemm_mx8_pair2")
+    elif rowsumsq is None:
         check(_lib_mx.lib.ltxmi_gemm_mx8(ctypes.byref(args), _stream()), "ltxmi_gemm_mx8")
     else:
         check(_lib_mxa.lib.ltxmi_gemm_mx8_rowsumsq(ctypes.byref(args), _ptr(rowsumsq), rowsumsq_cols, rowsumsq.stride(0), _stream()),

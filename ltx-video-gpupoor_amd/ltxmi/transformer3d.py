@@ -164,18 +164,23 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------ LoRA adapters (ltxmi/lora.py)
-    def attach_lora(self, adapter, weight: float = 1.0, name: Optional[str] = None, strict: bool = True):
+    def attach_lora(self, adapter, weight: float = 1.0, name: Optional[str] = None, strict: bool = True, mx8: bool = False):
         """Run ``adapter`` (``loading.load_lora``) unmerged on top of the base weights, at strength ``weight``; several
         adapters may be active at once.  Targets are the ten linears of every block.  An adapter that names another linear
         (patchify_proj, adaln_single.*, caption_projection.*, proj_out): ``strict=True`` raises and lists them,
-        ``strict=False`` skips them.  Returns the list of skipped linears.  The reference: inference.py:483-493."""
+        ``strict=False`` skips them.  Returns the list of skipped linears.  The reference: inference.py:483-493.
+        ``mx8=True``: the adapter may name linears that ``quantize_ff`` / ``quantize_attention`` run in MX-FP8 (with the default
+        that is refused); on those it runs as an MX-FP8 operand pair -- ``down``, ``T`` and ``bf16(s up)`` quantised, the K loop
+        of the linear's own call continued (``lora.pair_mx8``) -- and on every other linear in bf16 as before.  It works on
+        ``keep_bf16=False`` models.  The order is quantise, then attach; ``unquantize_*`` turns the pairs concerned into bf16 ones."""
         mine, other = lora.split_targets(adapter, len(self.transformer_blocks))
         if other and strict:
             raise ValueError("ltxmi: the adapter names linears outside the transformer blocks, which carry no adapter here: "
                              + ", ".join(other))
         lora.check_shapes(self, adapter, mine)
-        self._refuse_ff_quantized(mine.values(), "attach_lora")
-        self._refuse_attn_quantized(mine.values(), "attach_lora")
+        if not mx8:
+            self._refuse_ff_quantized(mine.values(), "attach_lora")
+            self._refuse_attn_quantized(mine.values(), "attach_lora")
         active = self.__dict__.setdefault("_lora_adapters", lora.OrderedDict())
         if name is None:
             name = f"lora{len(active)}"
@@ -352,6 +357,7 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         self._refuse_ff_freed("unquantize_ff")
         for b in self.transformer_blocks:
             b.ff.__dict__.pop("_mx8", None)
+        self._rebuild_mx8_lora()
 
     @property
     def ff_quantized(self) -> bool:
@@ -422,6 +428,15 @@ class Transformer3DModel(DerivedOwner, nn.Module):
         for attn in self._quantized_attentions():
             del attn.__dict__["_mx8"]
         self.__dict__.pop("_mx8_attn_linears", None)
+        self._rebuild_mx8_lora()
+
+    def _rebuild_mx8_lora(self):
+        """After an ``unquantize_*``: adapters attached with ``mx8=True`` to the linears concerned become bf16 pairs, as if
+        attached to the unquantised model.  Nothing is rebuilt (and no epoch moves) when no such pair exists."""
+        owners = [o for b in self.transformer_blocks for o in (b.ff, b.attn1, getattr(b, "attn2", None)) if o is not None]
+        if any(isinstance(s, lora.LoraSlotMx8) and not lora.runs_mx8(o, n)
+               for o in owners for n, s in (o.__dict__.get("_lora") or {}).items()):
+            lora.rebuild(self)
 
     @property
     def attention_quantized(self) -> bool:
